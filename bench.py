@@ -27,6 +27,9 @@ the timed region; `traffic` / `pmc` only from PMC summaries recorded at THIS sou
 standalone hook-body kernel over a rotation of activations larger than the Infinity Cache), `api` (the same prune
 through the reference-named Python API on a live module, engine build included) and `cpu_baseline` (the CPU oracle
 timed on this box's host cores, rank 0, N=1).
+
+`--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy (see dump_outputs), for comparing two builds
+output for output on the same seeded inputs.
 """
 from __future__ import annotations
 
@@ -501,6 +504,31 @@ def api_level(args, weights, calib, evalb, plan, dev, steps=5, search_batches=No
                     + " -> prune_vit_mlp_width(precomputed_importance) -> prune_vit_attention_blocks(selected_indices); engine build inside the bracket"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, out, targets):
+    """What the last timed step handed back, one .npy per array (float64 stays float64, everything else becomes float32):
+    `stage1_scores` [depth, d_int], `depth_impact` [depth] and per target `ffn_prune_mask_target<permille>` [depth, d_int]
+    (1 = pruned) and `selected_blocks_target<permille>` [K].  The weights and images are seeded, so two builds run with the
+    same arguments can be compared output for output.  Returns {name: shape}."""
+    import numpy as np
+    imps, impact, all_masks, chosen = out
+    arrays = {"stage1_scores": torch.stack([s.detach().cpu() for s in imps]), "depth_impact": impact}
+    for t, masks, blocks in zip(targets, all_masks, chosen):
+        tag = f"target{round(t * 1000):04d}"
+        arrays[f"ffn_prune_mask_{tag}"] = torch.stack([m.cpu() for m in masks])
+        arrays[f"selected_blocks_{tag}"] = torch.tensor(blocks)
+    arrays = {k: v.detach().cpu().to(torch.float64 if v.dtype == torch.float64 else torch.float32).numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -551,9 +579,16 @@ def main():
     ap.add_argument("--overlap-stage1", action="store_true",
                     help="stage 1 on a second HIP stream (own engine workspace) BESIDE the layer-major search on the main one; "
                          "unlike --two-streams the search keeps its layer-major form and its candidates are not shared out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (stage-1 scores, depth-search impacts, per target "
+                         "the FFN prune masks and the selected blocks) to DIR/<name>.npy; rank 0 only")
     args = ap.parse_args()
     if args.overlap_stage1 and args.two_streams:
         raise SystemExit("--overlap-stage1 and --two-streams are two forms of the same idea: pick one")
+    if args.dump_outputs and args.act_l2_only:
+        raise SystemExit("--dump-outputs needs the timed prune step; --act-l2-only runs none")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1: the result line is the time of the timed steps")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -761,6 +796,7 @@ def main():
     if prof is not None:
         prof.__exit__(None, None, None)
     coll = sdist.collective_ms() if sdist.TIMING else None
+    dumped = dump_outputs(args.dump_outputs, out, targets) if args.dump_outputs and rank == 0 else None
     if world > 1 or "RANK" in os.environ:
         # one line per rank on stderr: a failed or slow multi-rank run is then readable from the tail of the driver's log
         print(sdist.rank_summary({"local_ms_per_step": round(elapsed / args.steps * 1e3, 3), "steps": args.steps,
@@ -838,6 +874,8 @@ def main():
             "pass_stats": dict(core.PASS_STATS) if one_pass else None,
             "streams": 2 if (args.two_streams or args.overlap_stage1) else 1, "stage1_beside_search": bool(args.overlap_stage1), "search": "layer-major" if args.batch_candidates else "candidate-major",
         }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if one_card:
             line["rehearsal"] = f"{world} ranks share ONE card over gloo (SSP2_REHEARSE_ONE_CARD=1): a correctness rehearsal, not a scaling figure"
         if overlap is not None:

@@ -7,6 +7,7 @@ duck-typed modules of `oracle/vit_modules.py` on seeded inputs and writes DATA O
 reference's outputs) to `tests/golden/*.npz|*.json`.  No reference source text is stored.
 
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py --properties     # properties_reference.json + ref_head_*.pt of tests/test_properties_cpu.py
 """
 from __future__ import annotations
 
@@ -586,7 +587,65 @@ def preprocess_cases():
     print("[golden] preprocess_pil.npz written (Pillow", PIL.__version__, ")")
 
 
+def property_cases(n_planner=60, n_masks=60, n_oracle=25):
+    """The reference's outputs on fixed seeded cases of tests/test_properties_cpu.py -> properties_reference.json + ref_head_<kind>.pt.
+    The test module builds every case's inputs (imported from there, so both sides build the same ones) and runs the cases as explicit
+    examples; tensors are stored as the test's digests of dtype, shape and bits, inputs included (a torch whose module init differs is
+    caught instead of compared)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_properties_cpu as P
+    rng = np.random.default_rng(20261015)
+
+    def geometry(head_dims):
+        return dict(layout=str(rng.choice(["timm", "hf"])), heads=int(rng.choice([1, 2, 4])), head_dim=int(rng.choice(head_dims)))
+
+    out = {"made_by": "the reference's plan_2ssp_allocation, prune_vit_mlp_width, _compute_ffn_activation_importance, evaluate_top1, "
+                      "Auto2SSPInterface._compute_att_depth_importance and save_cifar_adapter (tests/golden/make_golden.py --properties)",
+           "planner": [], "mask_step": [], "oracle": []}
+    for i in range(n_planner):
+        a = dict(geometry([4, 8]), inter=int(rng.integers(6, 97)), depth=int(rng.integers(2, 10)), classes=int(rng.choice([3, 10])),
+                 target=round(float(rng.uniform(0.02, 0.95)), 4), min_remaining=int(rng.choice([0, 4, 16, 64])),
+                 forced=None if i % 2 else int(rng.integers(0, 11)))
+        m = P.tiny_model(a["layout"], a["heads"], a["head_dim"], a["inter"], a["depth"], a["classes"], 0)
+        plan = quiet(ref_vp.plan_2ssp_allocation, m, a["target"], min_remaining=a["min_remaining"], forced_blocks=a["forced"])
+        out["planner"].append({"args": a, "want": dict(plan.__dict__)})
+    for i in range(n_masks):
+        a = dict(geometry([4, 8]), inter=int(rng.integers(6, 97)), depth=int(rng.integers(2, 10)), classes=int(rng.choice([3, 10])),
+                 t=0 if i == 1 else int(rng.integers(0, 201)), min_remaining=int(rng.choice([1, 4, 16])),
+                 levels=1 if i == 0 else int(rng.integers(1, 41)), seed=int(rng.integers(0, 10 ** 6)))
+        m, imps, ts = P.mask_case(a["layout"], a["heads"], a["head_dim"], a["inter"], a["depth"], a["classes"], a["t"], a["levels"], a["seed"])
+        inputs = P.sha(*m.parameters(), *imps)
+        res = quiet(ref_vp.prune_vit_mlp_width, m, n_to_prune_per_block=list(ts), min_remaining=a["min_remaining"],
+                    precomputed_importance=[x.clone() for x in imps], collect_masks=True, device="cpu")
+        out["mask_step"].append({"args": a, "want": {"inputs": inputs, "masks": [list(map(int, x)) for x in res["ffn_prune_masks"]],
+                                                     "indices": [list(map(int, x)) for x in res["ffn_pruned_indices"]],
+                                                     "params": P.params_sha(res["model"])}})
+    torch.set_num_threads(2)                                # the thread count the test runs these forwards with
+    for i in range(n_oracle):
+        a = dict(geometry([8, 16]), inter=int(rng.integers(8, 81)), depth=1 if i == 2 else int(rng.integers(1, 6)),
+                 sizes=[int(x) for x in rng.integers(1, 8, size=int(rng.integers(1, 5)))],
+                 limit=0 if i == 0 else None if i % 3 == 1 else int(rng.integers(0, 6)), seed=int(rng.integers(0, 10 ** 6)))
+        m, batches = P.oracle_case(a["layout"], a["heads"], a["head_dim"], a["inter"], a["depth"], a["sizes"], a["seed"])
+        inputs = P.sha(*m.parameters(), *(t for b in batches for t in (b["pixel_values"], b["labels"])))
+        scores = quiet(ref_vp._compute_ffn_activation_importance, m, batches, device="cpu", batch_limit=a["limit"])
+        top1 = quiet(ref_vp.evaluate_top1, m, batches, device="cpu", max_batches=a["limit"])
+        att = None
+        if a["depth"] >= 2:
+            iface = ref_mc.Auto2SSPInterface(m, batches, device="cpu", importance_mode="copy", batch_limit=a["limit"] if a["limit"] is not None else 5)
+            att = P.sha(quiet(iface._compute_att_depth_importance))
+        out["oracle"].append({"args": a, "want": {"inputs": inputs, "scores": [P.sha(s) for s in scores], "top1": float(top1), "att": att}})
+    with open(os.path.join(HERE, "properties_reference.json"), "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+        f.write("\n")
+    for kind in ("linear", "adapter"):
+        ref_vp.save_cifar_adapter(P.head_source(kind), HERE, f"ref_head_{kind}.pt", extra={"note": 1})
+    print(f"[golden] properties_reference.json: {n_planner} planner, {n_masks} mask-step, {n_oracle} oracle cases; ref_head_{{linear,adapter}}.pt")
+
+
 if __name__ == "__main__":
+    if "--properties" in sys.argv:
+        property_cases()
+        sys.exit(0)
     if "--preprocess-only" in sys.argv:
         preprocess_cases()
         sys.exit(0)

@@ -533,6 +533,32 @@ def test_bench_self_launch_two_ranks_relays_rank0_line_and_failures():
     assert [json.loads(l) for l in out8.stdout.splitlines() if l.startswith("{")] == [{"metric": "launcher_selftest", "n_gpus": 8, "cuda_initialised": False}]
 
 
+def test_bench_dump_outputs_writes_what_the_step_returned(tmp_path):
+    """bench.py --dump-outputs: the last timed step's scores, impacts, masks and selections, one .npy each, float32 and equal to what
+    the step returned (float64 stays float64); past the size limit nothing is written."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    imps = [torch.rand(48, generator=g) for _ in range(3)]
+    impact = torch.rand(3, generator=g, dtype=torch.float64)
+    masks = [[(torch.rand(48, generator=g) > 0.5).to(torch.int16) for _ in range(3)] for _ in range(2)]
+    chosen = [[1], [0, 2]]
+    d = tmp_path / "out"
+    shapes = bench.dump_outputs(str(d), (imps, impact, masks, chosen), [0.25, 0.5])
+    assert shapes == {"stage1_scores": [3, 48], "depth_impact": [3], "ffn_prune_mask_target0250": [3, 48], "selected_blocks_target0250": [1],
+                      "ffn_prune_mask_target0500": [3, 48], "selected_blocks_target0500": [2]}
+    assert sorted(os.listdir(d)) == sorted(f"{k}.npy" for k in shapes)
+    got = {k: np.load(d / f"{k}.npy") for k in shapes}
+    assert got["depth_impact"].dtype == np.float64 and np.array_equal(got["depth_impact"], impact.numpy())
+    assert all(a.dtype == np.float32 for k, a in got.items() if k != "depth_impact")
+    assert np.array_equal(got["stage1_scores"], torch.stack(imps).numpy())
+    assert np.array_equal(got["ffn_prune_mask_target0500"], torch.stack(masks[1]).float().numpy())
+    assert got["selected_blocks_target0500"].tolist() == [0.0, 2.0]
+    big = [torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)]
+    with pytest.raises(SystemExit, match="limit"):
+        bench.dump_outputs(str(tmp_path / "big"), (big, impact, [[big[0].to(torch.int16)]], [[0]]), [0.5])
+    assert not (tmp_path / "big").exists()
+
+
 # ------------------------------------------------------------------------------------------ CLI --weights / --gpus
 def test_local_checkpoints_load_in_all_three_key_layouts(tmp_path):
     """weights.load_checkpoint (CLI --weights; reference auto_2ssp.py:636-667 loads with from_pretrained / timm): an HF-style

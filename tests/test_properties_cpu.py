@@ -1,44 +1,60 @@
 """Property tests (hypothesis; SURVEY.md §4 test plan item 3) of the host-side rows of §8: planner (f3), mask step (a7 / a8),
 stage-2 selection (a9), the dealing of batches over ranks (e).
 
-Where the REAL reference is importable (this build container: /root/reference; it never travels) every generated case is also run
-through the reference's own function and the results must be EQUAL — random geometries, scores with ties, clamps and forced
-block counts that the committed known-answer fixtures do not reach.  Elsewhere only the invariants are checked.
+The REAL reference's outputs on fixed seeded cases — random geometries, scores with ties, clamps, forced block counts and loaders
+that the other known-answer fixtures do not reach — are stored in tests/golden/properties_reference.json (written by
+`tests/golden/make_golden.py --properties`, the only code that imports the reference).  Every stored case runs as an explicit
+example of its test on every box, and there the results must EQUAL the reference's; the generated cases check the invariants.
 Derandomised: the same cases on every run; no example database is written.
 """
-import copy
+import hashlib
+import json
 import os
-import sys
 
 import pytest
 import torch
 
-from conftest import ROOT  # noqa: F401  (import paths)
+from conftest import GOLDEN
 
 hypothesis = pytest.importorskip("hypothesis")
-from hypothesis import given, settings, strategies as st  # noqa: E402
+from hypothesis import example, given, settings, strategies as st  # noqa: E402
 
-REF = "/root/reference"
-_ref_vp = None
+REF_CASES_PATH = os.path.join(GOLDEN, "properties_reference.json")
+# absent only while make_golden.py --properties imports this module to write it (test_the_reference_is_really_compared_where_it_exists)
+REF_CASES = json.load(open(REF_CASES_PATH)) if os.path.exists(REF_CASES_PATH) else {}
+_REF_INDEX = {name: {json.dumps(c["args"], sort_keys=True): c["want"] for c in cases}
+              for name, cases in REF_CASES.items() if isinstance(cases, list)}
 
 
-def ref_vp():
-    """The reference's src/vit_pruning module, or None where /root/reference does not exist (every box but the build container)."""
-    global _ref_vp
-    if _ref_vp is None:
-        p = os.path.join(REF, "adaptation-for-Pures-framework")
-        if not os.path.isdir(p):
-            _ref_vp = False
-        else:
-            sys.path.insert(0, p)
-            try:
-                from src import vit_pruning as m
-                _ref_vp = m
-            except Exception:                    # an ordinary import error: the invariants still run
-                _ref_vp = False
-            finally:
-                sys.path.remove(p)
-    return _ref_vp or None
+def reference_cases(name):
+    """Decorator: every stored case of `name` as an explicit example of the hypothesis test."""
+    def deco(fn):
+        for case in REF_CASES.get(name, []):
+            fn = example(**case["args"])(fn)
+        return fn
+    return deco
+
+
+def reference_output(name, **args):
+    """The reference's stored output for this case, or None for a generated case the fixture does not hold."""
+    return _REF_INDEX.get(name, {}).get(json.dumps(args, sort_keys=True))
+
+
+def sha(*tensors):
+    h = hashlib.sha256()
+    for t in tensors:
+        t = t.detach().contiguous()
+        h.update(f"{t.dtype}{tuple(t.shape)}".encode())
+        h.update(t.reshape(-1).view(torch.uint8).numpy().tobytes() if t.numel() else b"")
+    return h.hexdigest()
+
+
+def params_sha(model):
+    """One digest of every parameter's name, dtype, shape and bits, in module order (the reference's pruned weights)."""
+    h = hashlib.sha256()
+    for n, p in model.named_parameters():
+        h.update(n.encode() + sha(p).encode())
+    return h.hexdigest()
 
 
 def quiet(fn, *a, **k):
@@ -62,9 +78,10 @@ geometry = dict(layout=st.sampled_from(["timm", "hf"]), heads=st.sampled_from([1
 
 @CFG
 @given(target=st.floats(0.02, 0.95), min_remaining=st.sampled_from([0, 4, 16, 64]), forced=st.one_of(st.none(), st.integers(0, 10)), **geometry)
+@reference_cases("planner")
 def test_planner_invariants_and_equality_with_the_reference(layout, heads, head_dim, inter, depth, classes, target, min_remaining, forced):
     """`plan_2ssp_allocation` (reference src/vit_pruning.py:585-769): K stays below the depth, t respects the `min_remaining` clamp, the
-    bookkeeping fields are consistent — and every field equals the reference's on the same module."""
+    bookkeeping fields are consistent — and on a stored case every field equals the reference's on the same module."""
     from ssp2vit import vit_pruning as vp
     m = tiny_model(layout, heads, head_dim, inter, depth, classes, 0)
     plan = vp.plan_2ssp_allocation(m, target, min_remaining=min_remaining, forced_blocks=forced)
@@ -79,26 +96,33 @@ def test_planner_invariants_and_equality_with_the_reference(layout, heads, head_
     assert plan.estimated_total_removed_params == removed
     assert plan.est_error_params == abs(int(round(total * target)) - removed)
     assert plan.stage2_fraction == plan.blocks_to_prune / depth
-    r = ref_vp()
-    if r is not None:
-        want = quiet(r.plan_2ssp_allocation, m, target, min_remaining=min_remaining, forced_blocks=forced)
-        assert plan.__dict__ == want.__dict__
+    want = reference_output("planner", layout=layout, heads=heads, head_dim=head_dim, inter=inter, depth=depth, classes=classes,
+                            target=target, min_remaining=min_remaining, forced=forced)
+    if want is not None:
+        assert plan.__dict__ == want
+
+
+def mask_case(layout, heads, head_dim, inter, depth, classes, t, levels, seed):
+    """(module, importances, per-block prune counts) of one mask-step case."""
+    m = tiny_model(layout, heads, head_dim, inter, depth, classes, seed % 7)
+    g = torch.Generator().manual_seed(seed)
+    imps = [torch.randint(0, levels, (inter,), generator=g).float() for _ in range(depth)]
+    ts = [(t + 5 * b) % (inter + 20) for b in range(depth)]          # a different count per block, some beyond the clamp
+    return m, imps, ts
 
 
 @CFG
 @given(t=st.integers(0, 200), min_remaining=st.sampled_from([1, 4, 16]), levels=st.integers(1, 40), seed=st.integers(0, 10 ** 6), **geometry)
+@reference_cases("mask_step")
 def test_mask_step_with_ties_equals_the_reference(layout, heads, head_dim, inter, depth, classes, t, min_remaining, levels, seed):
     """a7 / a8 (reference :256-311) on importances drawn from `levels` distinct values — TIES at the cut are the rule, not the exception —
     with a different count per block, some beyond the `min_remaining` clamp, some zero: exactly n_prune ones per mask, no pruned score
-    above a kept one, the compacted fc1 is the kept rows in ascending order, an untouched block has no mask entry — and masks, index
-    lists and every weight tensor equal the reference's on a copy of the same module."""
+    above a kept one, the compacted fc1 is the kept rows in ascending order, an untouched block has no mask entry — and on a stored
+    case masks, index lists and every weight tensor equal the reference's on the same module."""
     from ssp2vit import vit_pruning as vp
-    m = tiny_model(layout, heads, head_dim, inter, depth, classes, seed % 7)
-    g = torch.Generator().manual_seed(seed)
-    imps = [torch.randint(0, levels, (inter,), generator=g).float() for _ in range(depth)]
-    m_ref = copy.deepcopy(m)
+    m, imps, ts = mask_case(layout, heads, head_dim, inter, depth, classes, t, levels, seed)
+    inputs = sha(*m.parameters(), *imps)
     fc1_before = [p.detach().clone() for n, p in m.named_parameters() if n.endswith(("fc1.weight", "intermediate.dense.weight"))]
-    ts = [(t + 5 * b) % (inter + 20) for b in range(depth)]          # a different count per block, some beyond the clamp
     out = quiet(vp.prune_vit_mlp_width, m, n_to_prune_per_block=list(ts), min_remaining=min_remaining, precomputed_importance=[i.clone() for i in imps],
                 collect_masks=True, device="cpu")
     drops = [max(0, min(ts[b], inter - min_remaining)) for b in range(depth)]
@@ -115,14 +139,13 @@ def test_mask_step_with_ties_equals_the_reference(layout, heads, head_dim, inter
         if drops[b] < inter:
             assert float(imps[b][mask_t.bool()].max()) <= float(imps[b][~mask_t.bool()].min())
         assert torch.equal(fc1_after[b], fc1_before[b][~mask_t.bool()])
-    r = ref_vp()
-    if r is not None:
-        want = quiet(r.prune_vit_mlp_width, m_ref, n_to_prune_per_block=list(ts), min_remaining=min_remaining,
-                     precomputed_importance=[i.clone() for i in imps], collect_masks=True, device="cpu")
-        assert [list(map(int, a)) for a in want["ffn_prune_masks"]] == [list(map(int, a)) for a in out["ffn_prune_masks"]]
-        assert [list(map(int, a)) for a in want["ffn_pruned_indices"]] == [list(map(int, a)) for a in out["ffn_pruned_indices"]]
-        for (na, pa), (nb, pb) in zip(want["model"].named_parameters(), out["model"].named_parameters()):
-            assert na == nb and torch.equal(pa, pb), na
+    want = reference_output("mask_step", layout=layout, heads=heads, head_dim=head_dim, inter=inter, depth=depth, classes=classes, t=t,
+                            min_remaining=min_remaining, levels=levels, seed=seed)
+    if want is not None:
+        assert inputs == want["inputs"], "this torch builds other modules / importances than the one that made the fixture"
+        assert want["masks"] == [list(map(int, a)) for a in out["ffn_prune_masks"]]
+        assert want["indices"] == [list(map(int, a)) for a in out["ffn_pruned_indices"]]
+        assert want["params"] == params_sha(out["model"])
 
 
 @CFG
@@ -170,56 +193,44 @@ def test_batches_are_dealt_to_ranks_without_loss_or_overlap(n, batch, world, lim
 
 
 def test_the_reference_is_really_compared_where_it_exists():
-    """The equality halves above must not vanish silently: where /root/reference is present its module has to import."""
-    if os.path.isdir(REF):
-        r = ref_vp()
-        assert r is not None and hasattr(r, "plan_2ssp_allocation") and hasattr(r, "prune_vit_mlp_width")
-        assert os.path.realpath(r.__file__).startswith(os.path.realpath(REF))
-        assert hasattr(r, "_compute_ffn_activation_importance") and hasattr(r, "evaluate_top1")
-    else:
-        assert ref_vp() is None
-
-
-_ref_mc = None
-
-
-def ref_mc():
-    """The reference's mask_conjunction module (Auto2SSPInterface), or None where /root/reference does not exist."""
-    global _ref_mc
-    if _ref_mc is None:
-        p = os.path.join(REF, "adaptation-for-Pures-framework")
-        if not os.path.isdir(p):
-            _ref_mc = False
-        else:
-            sys.path.insert(0, p)
-            try:
-                import mask_conjunction as m
-                _ref_mc = m
-            except Exception:
-                _ref_mc = False
-            finally:
-                sys.path.remove(p)
-    return _ref_mc or None
+    """The equality halves above must not vanish silently: the stored reference outputs are there, each test has its cases, and every
+    case names exactly the arguments of its test."""
+    import inspect
+    assert os.path.exists(REF_CASES_PATH)
+    for name, fn in (("planner", test_planner_invariants_and_equality_with_the_reference),
+                     ("mask_step", test_mask_step_with_ties_equals_the_reference),
+                     ("oracle", test_the_oracle_equals_the_reference_on_random_tiny_models)):
+        params = set(inspect.signature(fn.hypothesis.inner_test).parameters)
+        assert len(REF_CASES[name]) >= 25 and all(set(c["args"]) == params for c in REF_CASES[name]), name
+        assert len(_REF_INDEX[name]) == len(REF_CASES[name]), f"{name}: two stored cases with the same arguments"
 
 
 ORACLE_CFG = settings(max_examples=25, deadline=None, database=None, derandomize=True)
+
+
+def oracle_case(layout, heads, head_dim, inter, depth, sizes, seed):
+    """(module, batches) of one oracle-vs-reference case."""
+    m = tiny_model(layout, heads, head_dim, inter, depth, 10, seed % 5)
+    g = torch.Generator().manual_seed(seed)
+    batches = [{"pixel_values": torch.randn(n, 3, 32, 32, generator=g), "labels": torch.randint(0, 10, (n,), generator=g)} for n in sizes]
+    return m, batches
 
 
 @ORACLE_CFG
 @given(layout=st.sampled_from(["timm", "hf"]), heads=st.sampled_from([1, 2, 4]), head_dim=st.sampled_from([8, 16]), inter=st.integers(8, 80),
        depth=st.integers(1, 5), sizes=st.lists(st.integers(1, 7), min_size=1, max_size=4), limit=st.one_of(st.none(), st.integers(0, 5)),
        seed=st.integers(0, 10 ** 6))
+@reference_cases("oracle")
 def test_the_oracle_equals_the_reference_on_random_tiny_models(layout, heads, head_dim, inter, depth, sizes, limit, seed):
     """§8(c): the oracle (oracle/ref_cpu.py — the checker of every GPU parity test) against the reference ITSELF on geometries and
     loaders the committed fixtures do not hold: both anatomies, 1-5 blocks, ragged batches of 1-7 images, batch limits from 0 (no batch
-    at all) upwards.  Stage-1 scores in the reference's bf16 chain must be the same BITS and dtype, top-1 the same float, the
-    depth-importance vector the same tensor.  Without the reference (every box but the build container) the oracle's own
-    consistency is checked: a limit beyond the loader changes nothing, a limit of 0 gives zeros."""
+    at all) upwards.  On a stored case the stage-1 scores in the reference's bf16 chain must be the same BITS and dtype, top-1 the same
+    float, the depth-importance vector the same tensor.  On every case the oracle's own consistency is checked: a limit beyond the
+    loader changes nothing, a limit of 0 gives zeros."""
     from oracle import ref_cpu
     torch.set_num_threads(2)
-    m = tiny_model(layout, heads, head_dim, inter, depth, 10, seed % 5)
-    g = torch.Generator().manual_seed(seed)
-    batches = [{"pixel_values": torch.randn(n, 3, 32, 32, generator=g), "labels": torch.randint(0, 10, (n,), generator=g)} for n in sizes]
+    m, batches = oracle_case(layout, heads, head_dim, inter, depth, sizes, seed)
+    inputs = sha(*m.parameters(), *(t for b in batches for t in (b["pixel_values"], b["labels"])))
     imps = ref_cpu.ffn_activation_importance(m, batches, batch_limit=limit)
     acc = ref_cpu.evaluate_top1(m, batches, limit)
     assert len(imps) == depth and all(t.shape == (inter,) for t in imps)
@@ -228,25 +239,33 @@ def test_the_oracle_equals_the_reference_on_random_tiny_models(layout, heads, he
     if limit is not None and limit >= len(sizes):
         again = ref_cpu.ffn_activation_importance(m, batches, batch_limit=None)
         assert all(torch.equal(a, b) for a, b in zip(imps, again))
-    rv, rm = ref_vp(), ref_mc()
-    if rv is not None:
-        want = quiet(rv._compute_ffn_activation_importance, m, batches, device="cpu", batch_limit=limit)
-        for a, b in zip(want, imps):
-            assert a.dtype == b.dtype and torch.equal(a, b)
-        assert quiet(rv.evaluate_top1, m, batches, device="cpu", max_batches=limit) == acc
-    if rm is not None and depth >= 2:
-        iface = rm.Auto2SSPInterface(m, batches, device="cpu", importance_mode="copy", batch_limit=limit if limit is not None else 5)
-        want = quiet(iface._compute_att_depth_importance)
-        got = ref_cpu.att_depth_importance(m, batches, batch_limit=limit if limit is not None else 5)
-        assert want.dtype == got.dtype and torch.equal(want, got)
+    want = reference_output("oracle", layout=layout, heads=heads, head_dim=head_dim, inter=inter, depth=depth, sizes=sizes, limit=limit,
+                            seed=seed)
+    if want is not None:
+        assert inputs == want["inputs"], "this torch builds other modules / images than the one that made the fixture"
+        assert [sha(t) for t in imps] == want["scores"]                 # digest of dtype, shape and bits
+        assert acc == want["top1"]
+        if depth >= 2:
+            got = ref_cpu.att_depth_importance(m, batches, batch_limit=limit if limit is not None else 5)
+            assert sha(got) == want["att"]
 
 
 def test_the_reference_interface_is_really_compared_where_it_exists():
-    if os.path.isdir(REF):
-        m = ref_mc()
-        assert m is not None and hasattr(m, "Auto2SSPInterface") and os.path.realpath(m.__file__).startswith(os.path.realpath(REF))
-    else:
-        assert ref_mc() is None
+    """The reference's Auto2SSPInterface made the stored depth-importance vectors: every stored oracle case of two or more blocks has one."""
+    cases = REF_CASES["oracle"]
+    assert sum(c["args"]["depth"] >= 2 for c in cases) >= 10
+    assert all((c["want"]["att"] is not None) == (c["args"]["depth"] >= 2) for c in cases)
+
+
+def head_source(kind):
+    """The HF-layout model whose classifier head the head-file test saves: a Linear head, or the bottleneck adapter."""
+    import torch.nn as nn
+    src = tiny_model("hf", 2, 8, 24, 2, 10, seed=3)
+    if kind == "adapter":
+        torch.manual_seed(4)
+        src.classifier = nn.Sequential(nn.Linear(16, 5, bias=False), nn.GELU(), nn.Linear(5, 7, bias=True))
+        src.config.num_labels = 7
+    return src
 
 
 @pytest.mark.parametrize("kind", ["linear", "adapter"])
@@ -254,15 +273,10 @@ def test_classifier_head_files_round_trip_and_are_the_references(kind, tmp_path)
     """save_cifar_adapter / load_cifar_adapter (reference src/vit_pruning.py:774-875, in its `__all__`): the head of an HF-layout model — a
     Linear classifier or the bottleneck adapter Sequential(Linear(bias=False), GELU, Linear) — goes to one file and comes back onto another
     model with the same logits; the file's keys are the reference's; metadata missing from the file is read off the tensors; the three
-    RuntimeErrors.  Where the real reference is importable its loader must read THIS build's file and this loader the reference's, with
-    equal tensors."""
+    RuntimeErrors.  The file the REAL reference wrote for the same head (tests/golden/ref_head_<kind>.pt, make_golden.py --properties)
+    holds the same keys, metadata and tensors as THIS build's — what the reference's loader reads — and this loader reads it back."""
     from ssp2vit import vit_pruning as vp
-    import torch.nn as nn
-    src = tiny_model("hf", 2, 8, 24, 2, 10, seed=3)
-    if kind == "adapter":
-        torch.manual_seed(4)
-        src.classifier = nn.Sequential(nn.Linear(16, 5, bias=False), nn.GELU(), nn.Linear(5, 7, bias=True))
-        src.config.num_labels = 7
+    src = head_source(kind)
     path = vp.save_cifar_adapter(src, str(tmp_path), "head.pt", extra={"note": 1})
     blob = torch.load(path, map_location="cpu", weights_only=True)
     assert sorted(blob) == sorted(["state_dict", "classifier_type", "num_labels", "hidden_size", "timestamp", "extra"])
@@ -288,15 +302,11 @@ def test_classifier_head_files_round_trip_and_are_the_references(kind, tmp_path)
     torch.save({"state_dict": {}, "classifier_type": "Sequential"}, tmp_path / "empty_seq.pt")
     with pytest.raises(RuntimeError, match="reconstruct adapter"):
         vp.load_cifar_adapter(str(tmp_path / "empty_seq.pt"), tiny_model("hf", 2, 8, 24, 2, 3, seed=13))
-    R = ref_vp()
-    if R is not None:
-        theirs = tiny_model("hf", 2, 8, 24, 2, 3, seed=14)
-        R.load_cifar_adapter(path, theirs)                                  # the reference reads this build's file
-        assert torch.equal(theirs.classifier(feats), src.classifier(feats)) and theirs.config.num_labels == blob["num_labels"]
-        rpath = R.save_cifar_adapter(src, str(tmp_path), "ref_head.pt", extra={"note": 1})
-        rblob = torch.load(rpath, map_location="cpu", weights_only=True)
-        assert sorted(rblob) == sorted(blob) and all(torch.equal(rblob["state_dict"][k], blob["state_dict"][k]) for k in blob["state_dict"])
-        assert {k: rblob[k] for k in ("classifier_type", "num_labels", "hidden_size", "extra")} == {k: blob[k] for k in ("classifier_type", "num_labels", "hidden_size", "extra")}
-        ours = tiny_model("hf", 2, 8, 24, 2, 3, seed=15)
-        vp.load_cifar_adapter(rpath, ours)                                  # and this build reads the reference's
-        assert torch.equal(ours.classifier(feats), src.classifier(feats))
+    rpath = os.path.join(GOLDEN, f"ref_head_{kind}.pt")                 # the reference's file of the same head
+    rblob = torch.load(rpath, map_location="cpu", weights_only=True)
+    assert sorted(rblob) == sorted(blob) and sorted(rblob["state_dict"]) == sorted(blob["state_dict"])
+    assert all(torch.equal(rblob["state_dict"][k], blob["state_dict"][k]) for k in blob["state_dict"])
+    assert {k: rblob[k] for k in ("classifier_type", "num_labels", "hidden_size", "extra")} == {k: blob[k] for k in ("classifier_type", "num_labels", "hidden_size", "extra")}
+    ours = tiny_model("hf", 2, 8, 24, 2, 3, seed=15)
+    vp.load_cifar_adapter(rpath, ours)                                      # this build reads the reference's
+    assert torch.equal(ours.classifier(feats), src.classifier(feats)) and ours.config.num_labels == blob["num_labels"]
