@@ -132,6 +132,7 @@ struct ssp2_engine {
   unsigned int* attn_amax = nullptr;           // fp8 calibration: [depth] float bits of max |attention output| per block (ssp2_fp8_calibrate_*)
   bool fp8_calibrating = false;
   uint8_t* obuf8 = nullptr;                    // attention output as e4m3(o * 16) bytes: the A operand of the fp8 out-projection (SSP2_OPT_FP8_PROJ)
+  int o_ld = 0;                                // row stride of obuf / o_cls in elements (0: dim, what the forward uses; ssp2_attention_bf16 sets it)
   int ld8_dim = 0, ld8_int_max = 0;
   float* stage_f32 = nullptr;   // staging buffer of ssp2_load_tensor (host sources)
   size_t stage_cap = 0;
@@ -371,7 +372,7 @@ static int launch_attn_t(ssp2_engine* e, int n, RowMap rm, uint8_t* out8 = nullp
     HIPCHK(hipFuncSetAttribute((const void*)attn_fwd_kernel<DH, NT, CLS>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     attr_done[e->dev] = true;
   }
-  const int D = e->d.dim, ld = 3 * D;
+  const int D = e->d.dim, ld = 3 * D, ldo = e->o_ld > 0 ? e->o_ld : D;
   // algorithmic work of a full attention: S = QK^T and O = PV, 2 * N * N * d_h flops each per (image, head); q, k, v read, o written
   const double qn = CLS ? 1.0 : (double)e->tokens;
   ProfScope ps(e, SSP2_K_ATTN, 4.0 * qn * e->tokens * DH * e->d.heads * n, 2.0 * n * D * (2.0 * e->tokens + 2.0 * qn));
@@ -396,10 +397,10 @@ static int launch_attn_t(ssp2_engine* e, int n, RowMap rm, uint8_t* out8 = nullp
           lattr_done[e->dev] = true;
         }
         hipLaunchKernelGGL((attn64_persist_kernel<NT, (NT == 7 ? 1 : 0)>), dim3((unsigned)std::min<long>(items, e->n_cu)), dim3(512), psmem, e->stream, e->qkvbuf, ld,
-                           e->obuf, D, e->tokens, D, e->d.heads, (int)items, 1.0f / sqrtf((float)DH), rm, rev, e->opt[SSP2_OPT_ATTN_STAGGER], out8, e->ld8_dim, e->fp8_sat, out8_scale);
+                           e->obuf, ldo, e->tokens, D, e->d.heads, (int)items, 1.0f / sqrtf((float)DH), rm, rev, e->opt[SSP2_OPT_ATTN_STAGGER], out8, e->ld8_dim, e->fp8_sat, out8_scale);
       } else
       hipLaunchKernelGGL((attn64_persist_kernel<NT>), dim3((unsigned)std::min<long>(items, e->n_cu)), dim3(512), psmem, e->stream, e->qkvbuf, ld,
-                         e->obuf, D, e->tokens, D, e->d.heads, (int)items, 1.0f / sqrtf((float)DH), rm, rev, e->opt[SSP2_OPT_ATTN_STAGGER], out8, e->ld8_dim, e->fp8_sat, out8_scale);
+                         e->obuf, ldo, e->tokens, D, e->d.heads, (int)items, 1.0f / sqrtf((float)DH), rm, rev, e->opt[SSP2_OPT_ATTN_STAGGER], out8, e->ld8_dim, e->fp8_sat, out8_scale);
       HIPCHK(hipGetLastError());
       return 0;
     }
@@ -425,10 +426,10 @@ static int launch_attn_t(ssp2_engine* e, int n, RowMap rm, uint8_t* out8 = nullp
           lattr_done[e->dev] = true;
         }
         hipLaunchKernelGGL((attn80_persist_kernel<NT, 1>), dim3((unsigned)std::min<long>(items, e->n_cu)), dim3(512), psmem, e->stream, e->qkvbuf, ld,
-                           e->obuf, D, e->tokens, D, e->d.heads, (int)items, 1.0f / sqrtf((float)DH), rm, rev, e->opt[SSP2_OPT_ATTN_STAGGER], out8, e->ld8_dim, e->fp8_sat, out8_scale);
+                           e->obuf, ldo, e->tokens, D, e->d.heads, (int)items, 1.0f / sqrtf((float)DH), rm, rev, e->opt[SSP2_OPT_ATTN_STAGGER], out8, e->ld8_dim, e->fp8_sat, out8_scale);
       } else
       hipLaunchKernelGGL((attn80_persist_kernel<NT>), dim3((unsigned)std::min<long>(items, e->n_cu)), dim3(512), psmem, e->stream, e->qkvbuf, ld,
-                         e->obuf, D, e->tokens, D, e->d.heads, (int)items, 1.0f / sqrtf((float)DH), rm, rev, e->opt[SSP2_OPT_ATTN_STAGGER], out8, e->ld8_dim, e->fp8_sat, out8_scale);
+                         e->obuf, ldo, e->tokens, D, e->d.heads, (int)items, 1.0f / sqrtf((float)DH), rm, rev, e->opt[SSP2_OPT_ATTN_STAGGER], out8, e->ld8_dim, e->fp8_sat, out8_scale);
       HIPCHK(hipGetLastError());
       return 0;
     }
@@ -436,10 +437,10 @@ static int launch_attn_t(ssp2_engine* e, int n, RowMap rm, uint8_t* out8 = nullp
   if (out8) return fail(SSP2_ESTATE, "e4m3 attention output needs a persistent attention kernel (d_h = 64 / 80, SSP2_OPT_ATTN_PERSIST)");
   if (CLS)   // q from the compact CLS projection, only row 0 kept, compact [n, D] output
     hipLaunchKernelGGL((attn_fwd_kernel<DH, NT, true>), dim3(e->d.heads, n), dim3(256), smem, e->stream, e->qkvbuf, ld, e->q_cls,
-                       (size_t)D, 0, e->o_cls, (size_t)D, D, e->tokens, D, 1.0f / sqrtf((float)DH), rm);
+                       (size_t)D, 0, e->o_cls, (size_t)ldo, ldo, e->tokens, D, 1.0f / sqrtf((float)DH), rm);
   else
     hipLaunchKernelGGL((attn_fwd_kernel<DH, NT, false>), dim3(e->d.heads, n), dim3(256), smem, e->stream, e->qkvbuf, ld, e->qkvbuf,
-                       (size_t)e->tokens * ld, ld, e->obuf, (size_t)e->tokens * D, D, e->tokens, D, 1.0f / sqrtf((float)DH), rm);
+                       (size_t)e->tokens * ld, ld, e->obuf, (size_t)e->tokens * ldo, ldo, e->tokens, D, 1.0f / sqrtf((float)DH), rm);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1434,6 +1435,16 @@ int ssp2_act_l2_accum(void* stream, const void* act, int dtype, int n, int token
   return act_l2_impl(stream, act, dtype, n, RowMap{tokens, 0, 0}, d, ld, chain, group, norms_ws, out, out_stride);
 }
 
+// CUs of the current device, for the persistent kernels' grids of the operator entries below (asked once)
+static int op_cu_count() {
+  static int n_cu = 0;
+  if (!n_cu) {
+    int dev = 0; hipDeviceProp_t pr;
+    n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
+  }
+  return n_cu;
+}
+
 // The projection operator on its own (a3's building block): out = epilogue(A x W^T + bias) on caller-owned device
 // buffers, routed to the same two kernels as the forward (persistent 256 x 256 tiles for M >= 4096 rows, 128 x 128
 // otherwise; `kernel` = 1 / 2 forces the small / the large one — both give the same bits).
@@ -1443,13 +1454,8 @@ int ssp2_linear_bf16(void* hip_stream, int epilogue, const uint16_t* a_dev, int 
   if (M <= 0 || N <= 0 || K <= 0 || (K % GEMM_BK) || (N % 64)) return fail(SSP2_EINVAL, "linear: M=%d N=%d K=%d (K multiple of %d, N multiple of 64)", M, N, K, GEMM_BK);
   if (lda < K || ldw < K || (lda % 8) || (ldw % 8)) return fail(SSP2_EINVAL, "linear: lda=%d ldw=%d must be >= K and multiples of 8", lda, ldw);
   if (kernel < 0 || kernel > 2) return fail(SSP2_EINVAL, "kernel selector %d", kernel);
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0; hipDeviceProp_t pr;
-    n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-  }
   ssp2_engine e;
-  e.stream = (hipStream_t)hip_stream; e.n_cu = n_cu; e.dev = cur_device();
+  e.stream = (hipStream_t)hip_stream; e.n_cu = op_cu_count(); e.dev = cur_device();
   e.opt[SSP2_OPT_BIG_TILES] = e.opt[SSP2_OPT_FC1_BIG_TILES] = 1;
   e.opt[SSP2_OPT_BIG_TILE_MIN_ROWS] = kBigTileMinRowsDefault;
   { const char* v = getenv("SSP2_NT_STORES"); e.opt[SSP2_OPT_NT_STORES] = (v && *v) ? atoi(v) : 1; }      // the forward's default store policy
@@ -1472,7 +1478,7 @@ int ssp2_linear_bf16(void* hip_stream, int epilogue, const uint16_t* a_dev, int 
         const char* v = getenv("SSP2_DEFER_RESID");
         if (v && atoi(v)) {
           static unsigned int* park[kMaxDevices] = {};
-          if (!park[e.dev] && hipMalloc((void**)&park[e.dev], (size_t)n_cu * 131072) != hipSuccess) return fail(SSP2_ENOMEM, "linear: parking area");
+          if (!park[e.dev] && hipMalloc((void**)&park[e.dev], (size_t)e.n_cu * 131072) != hipSuccess) return fail(SSP2_ENOMEM, "linear: parking area");
           e.dg_scratch = park[e.dev];
           return launch_gemm256<EPI_RESID, 1>(&e, g, -2);
         }
@@ -1481,6 +1487,57 @@ int ssp2_linear_bf16(void* hip_stream, int epilogue, const uint16_t* a_dev, int 
       return big ? launch_gemm256<EPI_RESID>(&e, g, -2) : launch_gemm_small<EPI_RESID>(&e, g, -2);
     default: return fail(SSP2_EINVAL, "unknown epilogue %d", epilogue);
   }
+}
+
+// Multi-head attention on its own, on caller-owned buffers: a temporary engine with the forward's buffers pointed at the caller's,
+// then launch_attn — the routing and the instantiations of the forward (persistent / one-item kernel, LIVE, CLS-only tail).  Every
+// argument is checked before the device is touched.
+int ssp2_attention_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
+                        const uint16_t* q_cls_dev, uint16_t* out_dev, int ldo, uint8_t* out8_dev, int ldo8, float out8_scale,
+                        unsigned int* sat_dev, int persist, int live, int rev) {
+  if (!qkv_dev) return fail(SSP2_EINVAL, "attention: null qkv");
+  if (n <= 0 || heads <= 0 || tokens <= 0 || group < 0) return fail(SSP2_EINVAL, "attention: n=%d heads=%d tokens=%d group=%d", n, heads, tokens, group);
+  if (!attn_supported(d_h, tokens)) return fail(SSP2_EINVAL, "attention kernel not instantiated for d_h=%d, tokens=%d", d_h, tokens);
+  if ((long)heads * d_h > (1 << 20) || (heads * d_h) % 8) return fail(SSP2_EINVAL, "attention: dim = heads * d_h = %ld (a multiple of 8)", (long)heads * d_h);
+  const int dim = heads * d_h;
+  if (persist < -1 || persist > 1 || live < -1 || live > 1 || rev < 0 || rev > 1) return fail(SSP2_EINVAL, "attention: persist=%d live=%d rev=%d", persist, live, rev);
+  if (!out_dev && !out8_dev) return fail(SSP2_EINVAL, "attention: no output");
+  if (out_dev && (ldo < dim || ldo % 8)) return fail(SSP2_EINVAL, "attention: ldo=%d (>= dim %d, a multiple of 8)", ldo, dim);
+  if (q_cls_dev && (out8_dev || !out_dev)) return fail(SSP2_EINVAL, "attention: the CLS-only form writes bf16 only");
+  if (out8_dev && (ldo8 < dim || ldo8 % 16 || !(out8_scale > 0.f) || out8_scale > 65536.f)) return fail(SSP2_EINVAL, "attention: ldo8=%d out8_scale=%g", ldo8, out8_scale);
+  if ((long)n * heads > 0x7fffffffL) return fail(SSP2_EINVAL, "too many attention items");
+  ssp2_engine e;
+  e.d.dim = dim; e.d.heads = heads; e.tokens = tokens; e.dh = d_h;
+  e.opt[SSP2_OPT_ATTN_PERSIST] = persist < 0 ? 1 : persist;
+  e.opt[SSP2_OPT_ATTN_LIVE] = live < 0 ? 1 : live;
+  e.opt[SSP2_OPT_ZIGZAG] = 1; e.zig = rev;           // next_dir() hands the persistent kernels this direction
+  if (out8_dev && !attn_persistent(&e)) return fail(SSP2_EINVAL, "attention: the e4m3 output needs a persistent kernel (d_h = 64 with 97..224 tokens, d_h = 80 with 257)");
+  e.stream = (hipStream_t)hip_stream; e.n_cu = op_cu_count(); e.dev = cur_device();
+  e.qkvbuf = (bf16*)qkv_dev; e.q_cls = (bf16*)q_cls_dev;
+  e.obuf = e.o_cls = (bf16*)out_dev; e.o_ld = out_dev ? ldo : dim;
+  e.ld8_dim = ldo8; e.fp8_sat = sat_dev;
+  return launch_attn(&e, n, make_rowmap(tokens, n, group), q_cls_dev != nullptr, out8_dev, out8_scale);
+}
+
+// LayerNorm on its own, on caller-owned buffers: launch_ln of a temporary engine (the forward's MAXV / FULL dispatch and its
+// reverse-walk rule: `rev` takes effect from kBigTileMinRowsDefault rows on, as in the forward).
+int ssp2_layernorm(void* hip_stream, const float* x_dev, size_t in_stride, int rows, int D, const float* gamma_dev, const float* beta_dev,
+                   float eps, int gather_tokens, int gather_group, uint16_t* y_dev, int out_ld, uint8_t* y8_dev, float* ascale_dev, int rev) {
+  if (!x_dev || !gamma_dev || !beta_dev) return fail(SSP2_EINVAL, "layernorm: null operand");
+  if (rows <= 0 || D <= 0 || D % 4 || D > 2048) return fail(SSP2_EINVAL, "layernorm: rows=%d D=%d (D a multiple of 4, <= 2048)", rows, D);
+  if (!(eps >= 0.f) || !std::isfinite(eps)) return fail(SSP2_EINVAL, "layernorm: eps=%g", eps);
+  if (gather_tokens < 0 || gather_group < 0 || rev < 0 || rev > 1) return fail(SSP2_EINVAL, "layernorm: gather_tokens=%d gather_group=%d rev=%d", gather_tokens, gather_group, rev);
+  if (gather_tokens == 0 && (in_stride < (size_t)D || in_stride % 4)) return fail(SSP2_EINVAL, "layernorm: in_stride=%zu (>= D, a multiple of 4)", in_stride);
+  if (!y_dev == !y8_dev) return fail(SSP2_EINVAL, "layernorm: exactly one of y (bf16) and y8 (e4m3) is written");
+  if (y8_dev && !ascale_dev) return fail(SSP2_EINVAL, "layernorm: the e4m3 form writes per-row scales (ascale)");
+  if (out_ld < D || out_ld % 4) return fail(SSP2_EINVAL, "layernorm: out_ld=%d (>= D, a multiple of 4)", out_ld);
+  ssp2_engine e;
+  e.d.ln_eps = eps;
+  e.opt[SSP2_OPT_BIG_TILE_MIN_ROWS] = kBigTileMinRowsDefault;
+  e.opt[SSP2_OPT_ZIGZAG] = 1; e.zig = rev;
+  e.stream = (hipStream_t)hip_stream; e.dev = cur_device();
+  const RowMap gather = gather_tokens > 0 ? make_rowmap(gather_tokens, rows, gather_group) : RowMap{0, 0, 0};
+  return launch_ln(&e, x_dev, in_stride, gamma_dev, beta_dev, (bf16*)y_dev, out_ld, rows, D, gather, y8_dev, y8_dev ? ascale_dev : nullptr);
 }
 
 int ssp2_profile_begin(ssp2_handle e, int klass) {

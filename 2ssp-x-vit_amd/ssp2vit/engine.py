@@ -4,7 +4,7 @@ libssp2vit's HIP kernels.  There is no CPU path: constructing an engine without 
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -14,6 +14,15 @@ from ._lib import K_CLASS, OPTIONS, SCORE_CHAIN, SCORE_SITE, T_KINDS, Ssp2Error,
 
 def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def ssp2_rows(n: int, tokens: int, group: int = 0) -> int:
+    """Token-matrix rows of n images in the slab layout of `group` images per slab (csrc/engine.hip make_rowmap / total_rows)."""
+    if group <= 0 or group >= n:
+        return n * tokens
+    mpad = -(-group * tokens // _lib.SLAB_ALIGN) * _lib.SLAB_ALIGN
+    full, rest = divmod(n, group)
+    return full * mpad + rest * tokens if rest else (full - 1) * mpad + group * tokens
 
 
 class VitEngine:
@@ -405,6 +414,78 @@ class VitEngine:
                                         _ptr(wp), K, _ptr(bp), M, N, K, _ptr(out), N, _ptr(x if epi == 1 else None), N,
                                         {"auto": 0, "small": 1, "big": 2}[kernel]))
         return x if epi == 1 else out
+
+    def attention(self, qkv: torch.Tensor, n: int, tokens: int, heads: int, d_h: int, *, group: int = 0,
+                  out: Optional[torch.Tensor] = None, out8: Optional[torch.Tensor] = None, out8_scale: float = 16.0,
+                  sat: Optional[torch.Tensor] = None, q_cls: Optional[torch.Tensor] = None, persist: Optional[bool] = None,
+                  live: Optional[bool] = None, rev: int = 0) -> torch.Tensor:
+        """Multi-head attention of the forward on its own (ssp2_attention_bf16), on caller-owned buffers: qkv bf16
+        [>= rows, 3 * heads * d_h] densely packed, with rows = ssp2_rows(n, group).  Writes out (bf16 [>= rows, ldo], allocated when None) or,
+        with out8 (uint8 [>= rows, ldo8]), the fp8 mode's e4m3(o * out8_scale) bytes, counting clipping waves into sat (int32
+        [1]).  q_cls (bf16 [>= n, dim], densely packed): the CLS-only form, out [>= n, ldo].  persist / live override SSP2_OPT_ATTN_PERSIST /
+        SSP2_OPT_ATTN_LIVE (None: on); rev: walk direction of the persistent kernels.  Returns the tensor written."""
+        dim = heads * d_h
+        named = (("qkv", qkv, torch.bfloat16), ("out", out, torch.bfloat16), ("out8", out8, torch.uint8), ("q_cls", q_cls, torch.bfloat16))
+        for name, t, dt in named:
+            if t is not None and (t.device.type != "cuda" or t.dim() != 2 or t.dtype != dt or t.stride(1) != 1 or t.stride(0) < t.shape[1]):
+                raise ValueError(f"{name} must be a row-major 2-D {dt} device tensor")
+        if sat is not None and (sat.device.type != "cuda" or sat.dtype != torch.int32 or sat.numel() < 1):
+            raise ValueError("sat must be an int32 device tensor")
+        need = n if q_cls is not None else ssp2_rows(n, tokens, group)
+        # the kernels read qkv rows at a stride of 3 * dim and the compact CLS queries at a stride of dim: no other layout is accepted
+        if qkv.shape[1] != 3 * dim or qkv.stride(0) != 3 * dim or (q_cls is not None and (q_cls.shape[1] != dim or q_cls.stride(0) != dim)):
+            raise ValueError(f"qkv must be [rows, {3 * dim}] and q_cls [n, {dim}], densely packed (the kernels' row strides)")
+        if qkv.shape[0] < ssp2_rows(n, tokens, group) or (q_cls is not None and q_cls.shape[0] < n):
+            raise ValueError(f"qkv [{tuple(qkv.shape)}] / q_cls too small for n={n} tokens={tokens} heads={heads} d_h={d_h} group={group}")
+        if out is None and out8 is None:
+            out = torch.empty(need, dim, dtype=torch.bfloat16, device=qkv.device)
+        for t in (out, out8):
+            if t is not None and (t.shape[0] < need or t.shape[1] < dim):
+                raise ValueError(f"output [{tuple(t.shape)}] smaller than [{need}, {dim}]")
+        flag = {None: -1, False: 0, True: 1}
+        self._check(self.lib.ssp2_attention_bf16(C.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream), _ptr(qkv), n, tokens, heads, d_h,
+                                           group, _ptr(q_cls), _ptr(out), out.stride(0) if out is not None else 0, _ptr(out8),
+                                           out8.stride(0) if out8 is not None else 0, float(out8_scale), _ptr(sat), flag[persist], flag[live], int(rev)))
+        return out8 if out8 is not None else out
+
+    def layernorm(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, *, rows: Optional[int] = None,
+                  in_stride: Optional[int] = None, gather: Optional[Tuple[int, int]] = None, out: Optional[torch.Tensor] = None,
+                  ascale: Optional[torch.Tensor] = None, rev: int = 0) -> torch.Tensor:
+        """LayerNorm of the forward on its own (ssp2_layernorm), on caller-owned buffers: row r of x (f32) at r * in_stride
+        (default: x's row stride), or, gather = (tokens, group), the CLS row of image r in that layout.  D = gamma.numel().
+        out bf16 [>= rows, ld] (allocated when None) or uint8 [>= rows, ld] — the fp8 mode's per-row-scaled e4m3 bytes, with
+        the row scales (f32 [rows]) in ascale.  rev: walk direction (taken from 4096 rows on, as in the forward)."""
+        D = gamma.numel()
+        for name, t in (("x", x), ("gamma", gamma), ("beta", beta)):
+            if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous f32 device tensor")
+        if beta.numel() != D:
+            raise ValueError("gamma / beta sizes differ")
+        if rows is None:
+            rows = x.shape[0]
+        if gather is not None:
+            if x.dim() != 2 or x.shape[1] != D:                # the gather reads the CLS row of image r at row_of(r) * D
+                raise ValueError(f"the gathered form needs x as a [rows, {D}] token matrix")
+            if x.numel() < ssp2_rows(rows, gather[0], gather[1]) * D:
+                raise ValueError("x smaller than the gathered layout")
+            in_stride = 0
+        else:
+            in_stride = x.stride(0) if in_stride is None else int(in_stride)
+            if x.numel() < (rows - 1) * in_stride + D:
+                raise ValueError("x smaller than rows * in_stride")
+        if out is None:
+            out = torch.empty(rows, D, dtype=torch.bfloat16, device=x.device)
+        fp8 = out.dtype == torch.uint8
+        if (out.device.type != "cuda" or out.dim() != 2 or out.dtype not in (torch.bfloat16, torch.uint8) or out.stride(1) != 1
+                or out.shape[0] < rows or out.shape[1] < D):
+            raise ValueError(f"out must be a row-major bf16 / uint8 device tensor of >= [{rows}, {D}]")
+        if fp8 and (ascale is None or ascale.device.type != "cuda" or ascale.dtype != torch.float32 or ascale.numel() < rows):
+            raise ValueError("the e4m3 form needs ascale, f32 [rows] on the device")
+        gt, gg = gather if gather is not None else (0, 0)
+        self._check(self.lib.ssp2_layernorm(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), _ptr(x), in_stride, rows, D,
+                                      _ptr(gamma), _ptr(beta), float(eps), gt, gg, None if fp8 else _ptr(out), out.stride(0),
+                                      _ptr(out) if fp8 else None, _ptr(ascale) if fp8 else None, int(rev)))
+        return out
 
     # ------------------------------------------------------------------ compositions used by the host API
     def forward_scores(self, pixels: torch.Tensor, score_site: str, score_chain: str = "fp32",

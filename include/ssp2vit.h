@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SSP2_ABI_VERSION 5
+#define SSP2_ABI_VERSION 6
 
 enum {
   SSP2_OK = 0,
@@ -259,6 +259,32 @@ int ssp2_act_l2_accum(void* hip_stream, const void* act_dev, int dtype, int n, i
 enum { SSP2_EPI_BF16 = 0, SSP2_EPI_RESID = 1, SSP2_EPI_GELU = 2 };
 int ssp2_linear_bf16(void* hip_stream, int epilogue, const uint16_t* a_dev, int lda, const uint16_t* w_dev, int ldw,
                      const float* bias_dev, int M, int N, int K, uint16_t* out_dev, int ldo, float* x_dev, int ldx, int kernel);
+
+/* Multi-head self-attention on its own, on caller-owned device buffers: the kernel the forward launches for this geometry, with
+ * its routing (persistent / one-item kernel, the compile-time-padding LIVE form, the CLS-only tail).
+ *   qkv_dev bf16 [rows, 3 * dim] in the engine's [row][q | k | v][head][d_h] layout, dim = heads * d_h; rows = ssp2_rows of
+ *   (n, group) (group: the slab layout; 0 = images contiguous).  Rows that are no image's (slab padding) are never read.
+ *   out_dev bf16 [rows, ldo] = softmax(q k^T / sqrt(d_h)) v per head: fp32 scores, exp2 of fma(s, c2, -max * c2) with
+ *   c2 = log2(e) / sqrt(d_h), P rounded to bf16 for P V, fp32 row sum, one bf16 rounding of the output (csrc/attn.hip.h).
+ *   Only the image rows, columns [0, dim), are written.
+ *   q_cls_dev != NULL: the CLS-only form of ssp2_tail — q_cls_dev bf16 [n, dim] compact CLS queries, out_dev [n, ldo] compact.
+ *   out8_dev != NULL: the fp8 mode's output instead of out_dev (which may be NULL), e4m3(o * out8_scale) bytes [rows, ldo8],
+ *   ldo8 % 16 == 0; every wave that clipped a value adds 1 to *sat_dev (may be NULL).  Needs a persistent kernel.
+ *   persist / live: SSP2_OPT_ATTN_PERSIST / SSP2_OPT_ATTN_LIVE for this call (-1 = default, on); rev: walk direction of the
+ *   persistent kernels (0 / 1).  A geometry without a kernel is SSP2_EINVAL. */
+int ssp2_attention_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
+                        const uint16_t* q_cls_dev, uint16_t* out_dev, int ldo, uint8_t* out8_dev, int ldo8, float out8_scale,
+                        unsigned int* sat_dev, int persist, int live, int rev);
+
+/* LayerNorm over the last dim on its own, on caller-owned device buffers: the forward's launch (one instantiation per 256-wide
+ * step of D, the unpredicated form where D = 256 * MAXV, the reverse walk from 4096 rows on when rev = 1).
+ *   x_dev f32, row r at x_dev + r * in_stride (in_stride % 4 == 0); or, gather_tokens > 0, the CLS row of image r in the
+ *   layout (gather_tokens, gather_group) of ssp2_rows (the classifier head's form; in_stride unused).  gamma / beta f32 [D].
+ *   D % 4 == 0, D <= 2048.  Two-pass fp32 mean / variance, rstd = 1 / sqrt(var + eps), y = (x - mean) * rstd * gamma + beta.
+ *   y_dev != NULL: bf16 [rows, out_ld].  y8_dev != NULL (instead): the fp8 mode's per-row-scaled output, e4m3(bf16(y) / ascale)
+ *   bytes [rows, out_ld] with ascale_dev[r] = max|bf16(y)| / 448 of the row (1 for a zero row).  out_ld % 4 == 0. */
+int ssp2_layernorm(void* hip_stream, const float* x_dev, size_t in_stride, int rows, int D, const float* gamma_dev, const float* beta_dev,
+                   float eps, int gather_tokens, int gather_group, uint16_t* y_dev, int out_ld, uint8_t* y8_dev, float* ascale_dev, int rev);
 
 /* f4 — input pipeline on the device, the step in front of the path (adaptation-for-Pures-framework/auto_2ssp.py:
  * 290-301): uint8 HWC images -> bicubic resize to out x out (Pillow's 8-bit fixed-point resampler, bit-identical) ->

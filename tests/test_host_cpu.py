@@ -252,6 +252,51 @@ def test_library_exports_every_declared_symbol():
     assert lib.ssp2_abi_version() == _lib.ABI_VERSION
 
 
+def test_operator_entries_refuse_bad_arguments_before_touching_the_device():
+    """ssp2_attention_bf16 / ssp2_layernorm check every argument before the first HIP call: each call below must come back
+    SSP2_EINVAL with a message, on a machine without a GPU too.  The pointers are never dereferenced (a dummy address)."""
+    import ctypes as C
+    from ssp2vit import _lib
+    from ssp2vit.engine import VitEngine, ssp2_rows
+    lib = _lib.load()
+    P = C.c_void_p(4096)
+
+    def attn(qkv=P, n=2, tokens=197, heads=12, d_h=64, group=0, q_cls=None, out=P, ldo=768, out8=None, ldo8=0, scale=16.0,
+             persist=-1, live=-1, rev=0):
+        return lib.ssp2_attention_bf16(None, qkv, n, tokens, heads, d_h, group, q_cls, out, ldo, out8, ldo8, scale, None, persist, live, rev)
+    bad_attn = [dict(qkv=None), dict(n=0), dict(heads=0), dict(tokens=0), dict(group=-1),
+                dict(d_h=64, tokens=289), dict(d_h=80, tokens=256, ldo=960), dict(d_h=16, tokens=33, ldo=192), dict(d_h=32, tokens=50, ldo=384),
+                dict(d_h=80, tokens=257, heads=1, ldo=72),
+                dict(ldo=767), dict(ldo=772), dict(out=None), dict(persist=2), dict(live=-2), dict(rev=2),
+                dict(q_cls=P, out8=P, ldo8=768), dict(out=None, out8=P, ldo8=776), dict(out=None, out8=P, ldo8=768, scale=0.0),
+                dict(out=None, out8=P, ldo8=768, tokens=50), dict(out=None, out8=P, ldo8=768, persist=0),
+                dict(out=None, out8=P, ldo8=1280, d_h=80, heads=16, tokens=260, ldo=1280)]
+    for kw in bad_attn:
+        assert attn(**kw) == -1, kw
+        assert lib.ssp2_last_error(), kw
+
+    def ln(x=P, in_stride=768, rows=4, D=768, g=P, b=P, eps=1e-6, gt=0, gg=0, y=P, out_ld=768, y8=None, ascale=None, rev=0):
+        return lib.ssp2_layernorm(None, x, in_stride, rows, D, g, b, eps, gt, gg, y, out_ld, y8, ascale, rev)
+    bad_ln = [dict(x=None), dict(g=None), dict(b=None), dict(rows=0), dict(D=0), dict(D=770, in_stride=770, out_ld=772),
+              dict(D=2052, in_stride=2052, out_ld=2052), dict(eps=-1.0), dict(eps=float("nan")), dict(eps=float("inf")),
+              dict(in_stride=764), dict(in_stride=770), dict(gt=-1), dict(gg=-1), dict(rev=2), dict(y=None),
+              dict(y8=P, ascale=P), dict(y=None, y8=P), dict(out_ld=766), dict(out_ld=770)]
+    for kw in bad_ln:
+        assert ln(**kw) == -1, kw
+        assert lib.ssp2_last_error(), kw
+
+    # the wrappers refuse host tensors and undersized buffers before any call (an engine object without a device)
+    eng = VitEngine.__new__(VitEngine)
+    eng.lib = lib
+    with pytest.raises(ValueError):
+        eng.attention(torch.zeros(2 * 197, 3 * 768, dtype=torch.bfloat16), 2, 197, 12, 64)
+    with pytest.raises(ValueError):
+        eng.layernorm(torch.zeros(4, 768), torch.ones(768), torch.zeros(768), 1e-6)
+    # slab rows: the layout of csrc/engine.hip (group < n: slabs padded to 128 rows, the last one unpadded)
+    assert ssp2_rows(5, 197) == 985 and ssp2_rows(5, 197, 5) == 985 and ssp2_rows(5, 197, 2) == 2 * 512 + 197
+    assert ssp2_rows(4, 197, 2) == 512 + 394 and ssp2_rows(3, 50, 1) == 2 * 128 + 50
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
 def test_product_path_fails_loudly_without_gpu():
     from oracle.vit_modules import build_from_flat
