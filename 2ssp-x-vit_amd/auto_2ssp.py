@@ -78,6 +78,7 @@ def run_one(args, target, run_id):
     pg = _process_group()
     rank0 = pg is None or torch.distributed.get_rank() == 0
     vp.DEFAULT_PRECISION = "bf16"          # (module-level switch: a previous fp8 run in this process must not leak into this one's set-up)
+    vp.DEFAULT_ATTN_STREAM = 1 if args.long_sequences else None      # None: the environment's SSP2_ATTN_STREAM
     if args.weights:
         # a LOCAL checkpoint (reference :636-667 loads its model with from_pretrained / timm.create_model; the network
         # fetches stay out): .safetensors / .pth state dict or an HF save_pretrained directory, any of the three key layouts
@@ -331,6 +332,9 @@ def build_argparser():
                    help="fp8: QKV / out-proj / fc1 / fc2 of launches with >= 4096 token rows on e4m3 MFMA operands (opt-in tolerance mode, configs[4])")
     p.add_argument("--two-pass", action="store_true", help="compute the two importances in two separate walks over the calibration loader, as the reference "
                                                            "does (default: one walk whose dense forward serves both; a reshuffling loader then feeds both stages the same order)")
+    p.add_argument("--long-sequences", action="store_true",
+                   help="models with more than 288 tokens (384-pixel /16: 577, patch 8: 785) on the key-streaming attention kernel "
+                        "(the engines' attn_stream = 1, as SSP2_ATTN_STREAM=1); without it such a model is refused when its engine is created")
     p.add_argument("--fp8-calibrate", action="store_true", help="with --precision fp8: measure the attention outputs of the first calibration images and set the e4m3 hand-off scales")
     # accepted and ignored (data / fine-tuning flags of the reference that need the network)
     for flag in ("--load-cifar", "--do-finetune", "--freeze-backbone", "--replace-classifier", "--use-adapter", "--save-adapter",

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "attn.hip.h"
+#include "attn_stream.hip.h"
 #include "gemm256.hip.h"
 #include "misc.hip.h"
 #include "patch.hip.h"
@@ -445,18 +446,58 @@ static int launch_attn_t(ssp2_engine* e, int n, RowMap rm, uint8_t* out8 = nullp
   return 0;
 }
 
-// which geometries have a persistent kernel (the ones that can write the e4m3 output)
-static bool attn_persistent(const ssp2_engine* e) {
-  const int nt = (e->tokens + 31) / 32;
-  return e->opt[SSP2_OPT_ATTN_PERSIST] && ((e->dh == 64 && nt >= 4 && nt <= 7) || (e->dh == 80 && nt == 9 && e->tokens == 257));
-}
-// (head dim, 32-key tiles) pairs launch_attn below has an instantiation for — checked when an engine is created, so that an
-// unsupported geometry fails THERE and not at the first forward
-static bool attn_supported(int dh, int tokens) {
+static_assert(ATTN_STREAM_MAX_TOKENS == SSP2_ATTN_STREAM_MAX_TOKENS, "attn_stream.hip.h and ssp2vit.h state the same maximum");
+// (head dim, 32-key tiles) pairs of the resident kernels (attn.hip.h): K, V and a query's score row fit LDS / registers
+static bool attn_resident(int dh, int tokens) {
   const int nt = (tokens + 31) / 32;
   return (dh == 64 && nt >= 1 && nt <= 9) || (dh == 80 && nt == 9) || (dh == 16 && nt == 1);
 }
+static bool attn_stream_ok(int dh, int tokens) { return dh == 64 && tokens >= 1 && tokens <= ATTN_STREAM_MAX_TOKENS; }
+// SSP2_OPT_ATTN_STREAM: 1 = sequences without a resident kernel stream, 2 = every d_h = 64 attention streams
+static bool attn_streams(int mode, int dh, int tokens) {
+  return attn_stream_ok(dh, tokens) && (mode >= 2 || (mode == 1 && !attn_resident(dh, tokens)));
+}
+// which geometries have a persistent kernel (the ones that can write the e4m3 output); never the streaming route
+static bool attn_persistent(const ssp2_engine* e) {
+  const int nt = (e->tokens + 31) / 32;
+  if (attn_streams(e->opt[SSP2_OPT_ATTN_STREAM], e->dh, e->tokens)) return false;
+  return e->opt[SSP2_OPT_ATTN_PERSIST] && ((e->dh == 64 && nt >= 4 && nt <= 7) || (e->dh == 80 && nt == 9 && e->tokens == 257));
+}
+// geometries launch_attn below has a kernel for under the streaming mode `stream` — checked when an engine is created, so that an
+// unsupported geometry fails THERE and not at the first forward
+static bool attn_supported(int dh, int tokens, int stream = 0) {
+  return attn_resident(dh, tokens) || attn_streams(stream, dh, tokens);
+}
+// the key-streaming kernels (attn_stream.hip.h): full attention over the slab / dense rows, or the CLS-only tail
+static int launch_attn_stream(ssp2_engine* e, int n, RowMap rm, bool cls_only) {
+  const int D = e->d.dim, ld = 3 * D, ldo = e->o_ld > 0 ? e->o_ld : D, T = e->tokens;
+  const double qn = cls_only ? 1.0 : (double)T;
+  ProfScope ps(e, SSP2_K_ATTN, 4.0 * qn * T * 64 * e->d.heads * n, 2.0 * n * D * (2.0 * T + 2.0 * qn));
+  const long items = (long)e->d.heads * n;
+  const float scale = 1.0f / sqrtf(64.0f);
+  if (cls_only) {
+    if ((items + 3) / 4 > 0x7fffffffL) return fail(SSP2_EINVAL, "too many attention items");
+    hipLaunchKernelGGL(attn64_stream_cls_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, e->stream, e->qkvbuf, ld, e->q_cls, (size_t)D,
+                       e->o_cls, (size_t)ldo, T, D, e->d.heads, (int)items, scale, rm);
+  } else {
+    const int qblocks = (T + 32 * ATTN_STREAM_QW - 1) / (32 * ATTN_STREAM_QW);
+    if (items * qblocks > 0x7fffffffL) return fail(SSP2_EINVAL, "too many attention items");
+    static bool attr_done[kMaxDevices] = {};
+    if (!attr_done[e->dev]) {
+      HIPCHK(hipFuncSetAttribute((const void*)attn64_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_STREAM_SMEM));
+      attr_done[e->dev] = true;
+    }
+    hipLaunchKernelGGL(attn64_stream_kernel, dim3((unsigned)(items * qblocks)), dim3(64 * (ATTN_STREAM_QW + 1)), ATTN_STREAM_SMEM, e->stream,
+                       e->qkvbuf, ld, e->obuf, ldo, T, D, e->d.heads, qblocks, scale, rm);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 static int launch_attn(ssp2_engine* e, int n, RowMap rm, bool cls_only = false, uint8_t* out8 = nullptr, float out8_scale = ATTN_OUT8_SCALE) {
+  if (attn_streams(e->opt[SSP2_OPT_ATTN_STREAM], e->dh, e->tokens)) {
+    if (out8) return fail(SSP2_ESTATE, "the key-streaming attention writes bf16 only (no e4m3 output)");
+    return launch_attn_stream(e, n, rm, cls_only);
+  }
   const int nt = (e->tokens + 31) / 32;
 #define ATTN_CASE(DH_, NT_) if (e->dh == DH_ && nt == NT_) return cls_only ? launch_attn_t<DH_, NT_, true>(e, n, rm) : launch_attn_t<DH_, NT_, false>(e, n, rm, out8, out8_scale)
   ATTN_CASE(64, 7);   // 224/16: 197 tokens (Ti/S/B/L)
@@ -485,8 +526,15 @@ extern "C" {
 int ssp2_abi_version(void) { return SSP2_ABI_VERSION; }
 const char* ssp2_last_error(void) { return g_err.c_str(); }
 
-int ssp2_create(const ssp2_vit_desc* desc, ssp2_handle* out) {
+int ssp2_create(const ssp2_vit_desc* desc, ssp2_handle* out) { return ssp2_create_opts(desc, nullptr, out); }
+
+int ssp2_create_opts(const ssp2_vit_desc* desc, const int32_t* opt, ssp2_handle* out) {
   if (!desc || !out || !desc->d_int) return fail(SSP2_EINVAL, "null argument");
+  if (opt) {
+    for (int i = 0; i < SSP2_OPT_COUNT; ++i)
+      if (opt[i] < -1) return fail(SSP2_EINVAL, "option %d: override %d (-1 = environment default)", i, opt[i]);
+    if (opt[SSP2_OPT_ATTN_STREAM] > 2) return fail(SSP2_EINVAL, "SSP2_OPT_ATTN_STREAM takes 0, 1 or 2");
+  }
   const ssp2_vit_desc& d = *desc;
   if (d.img <= 0 || d.patch <= 0 || d.img % d.patch) return fail(SSP2_EINVAL, "img %d not divisible by patch %d", d.img, d.patch);
   if (d.dim <= 0 || d.dim % 64 || d.dim > 2048) return fail(SSP2_EINVAL, "dim %d must be a multiple of 64, <= 2048", d.dim);
@@ -530,6 +578,19 @@ int ssp2_create(const ssp2_vit_desc* desc, ssp2_handle* out) {
 #else
     e->opt[SSP2_OPT_DEFER_RESID] = 0;
 #endif
+    e->opt[SSP2_OPT_ATTN_STREAM] = std::max(0, std::min(2, env_int("SSP2_ATTN_STREAM", 0)));
+  }
+  if (opt) {   // explicit overrides go through the same checks as ssp2_set_option (the geometry is not known yet: checked below)
+    for (int i = 0; i < SSP2_OPT_COUNT; ++i) {
+      if (opt[i] < 0) continue;
+      const int v = opt[i];
+      bool bad = (i == SSP2_OPT_LN_FUSION && v > 2) || (i == SSP2_OPT_BIG_TILE_MIN_ROWS && v < 256);
+#ifndef SSP2_LAB
+      bad = bad || ((i == SSP2_OPT_LN_FUSION || i == SSP2_OPT_DEFER_RESID || i == SSP2_OPT_GROUP256) && v != 0);
+#endif
+      if (bad) { delete e; return fail(SSP2_EINVAL, "option %d: override %d not accepted", i, v); }
+      e->opt[i] = v;
+    }
   }
   e->d_int.assign(d.d_int, d.d_int + d.depth);
   e->d.d_int = e->d_int.data();
@@ -543,10 +604,15 @@ int ssp2_create(const ssp2_vit_desc* desc, ssp2_handle* out) {
     delete e;
     return fail(SSP2_EINVAL, "head dim %d unsupported (16, 64, 80)", d.dim / d.heads);
   }
-  if (!attn_supported(e->dh, e->tokens)) {
+  if (!attn_supported(e->dh, e->tokens, e->opt[SSP2_OPT_ATTN_STREAM])) {
     const int dh = e->dh, tk = e->tokens;
     delete e;
-    return fail(SSP2_EINVAL, "no attention kernel for head dim %d with %d tokens (head dim 64: up to 288 tokens; 80: 257..288; 16: up to 32)", dh, tk);
+    if (attn_stream_ok(dh, tk))
+      return fail(SSP2_EINVAL, "no resident attention kernel for head dim %d with %d tokens (head dim 64: up to 288 tokens); the key-streaming "
+                               "kernel takes it when opted in: SSP2_OPT_ATTN_STREAM = 1 (environment SSP2_ATTN_STREAM=1, VitEngine(attn_stream=1), "
+                               "CLI --long-sequences)", dh, tk);
+    return fail(SSP2_EINVAL, "no attention kernel for head dim %d with %d tokens (head dim 64: up to 288 tokens, up to %d with SSP2_OPT_ATTN_STREAM; "
+                             "80: 257..288; 16: up to 32)", dh, tk, ATTN_STREAM_MAX_TOKENS);
   }
   int rc = 0;
 #define TRY(x) do { if ((rc = (x))) { ssp2_destroy(e); return rc; } } while (0)
@@ -707,6 +773,12 @@ int ssp2_set_option(ssp2_handle e, int option, int value) {
     return fail(SSP2_ESTATE, "option %d (LayerNorm fusion / deferred residual / column-group tile order) exists in the lab build only: "
                              "lib/libssp2vit_lab.so (scripts/build_variant.py lab -DSSP2_LAB=1; VitEngine(lib_variant=\"lab\"))", option);
 #endif
+  if (option == SSP2_OPT_ATTN_STREAM) {
+    if (value < 0 || value > 2) return fail(SSP2_EINVAL, "SSP2_OPT_ATTN_STREAM takes 0, 1 or 2");
+    if (!attn_supported(e->dh, e->tokens, value))
+      return fail(SSP2_ESTATE, "SSP2_OPT_ATTN_STREAM = %d: head dim %d with %d tokens has no resident attention kernel", value, e->dh, e->tokens);
+    if (e->fp8 && attn_streams(value, e->dh, e->tokens)) return fail(SSP2_ESTATE, "SSP2_OPT_ATTN_STREAM = %d: the key-streaming attention is bf16 only (engine is in fp8)", value);
+  }
   e->opt[option] = value;
   return 0;
 }
@@ -907,6 +979,9 @@ int ssp2_set_precision(ssp2_handle e, int mode) {
   if (!e) return fail(SSP2_EINVAL, "null handle");
   if (mode == SSP2_PREC_BF16) { e->fp8 = false; return 0; }
   if (mode != SSP2_PREC_FP8) return fail(SSP2_EINVAL, "unknown precision %d", mode);
+  if (attn_streams(e->opt[SSP2_OPT_ATTN_STREAM], e->dh, e->tokens))
+    return fail(SSP2_ESTATE, "set_precision(fp8): this engine runs the key-streaming attention (SSP2_OPT_ATTN_STREAM = %d, %d tokens), which is bf16 only",
+                e->opt[SSP2_OPT_ATTN_STREAM], e->tokens);
   int rc;
   for (int l = 0; l < e->d.depth; ++l) {
     Layer& L = e->layers[l];
@@ -1517,6 +1592,26 @@ int ssp2_attention_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int to
   e.obuf = e.o_cls = (bf16*)out_dev; e.o_ld = out_dev ? ldo : dim;
   e.ld8_dim = ldo8; e.fp8_sat = sat_dev;
   return launch_attn(&e, n, make_rowmap(tokens, n, group), q_cls_dev != nullptr, out8_dev, out8_scale);
+}
+
+// The key-streaming attention on its own (attn_stream.hip.h), on caller-owned buffers; every argument checked before the device.
+int ssp2_attention_stream_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
+                               const uint16_t* q_cls_dev, uint16_t* out_dev, int ldo) {
+  if (!qkv_dev || !out_dev) return fail(SSP2_EINVAL, "attention_stream: null qkv / out");
+  if (n <= 0 || heads <= 0 || group < 0) return fail(SSP2_EINVAL, "attention_stream: n=%d heads=%d group=%d", n, heads, group);
+  if (d_h != 64) return fail(SSP2_EINVAL, "attention_stream: d_h=%d (64 only)", d_h);
+  if (tokens <= 0 || tokens > ATTN_STREAM_MAX_TOKENS) return fail(SSP2_EINVAL, "attention_stream: tokens=%d (1..%d)", tokens, ATTN_STREAM_MAX_TOKENS);
+  if ((long)heads * d_h > (1 << 20)) return fail(SSP2_EINVAL, "attention_stream: dim = heads * d_h = %ld", (long)heads * d_h);
+  const int dim = heads * d_h;
+  if (ldo < dim || ldo % 8) return fail(SSP2_EINVAL, "attention_stream: ldo=%d (>= dim %d, a multiple of 8)", ldo, dim);
+  if ((long)n * heads * ((tokens + 32 * ATTN_STREAM_QW - 1) / (32 * ATTN_STREAM_QW)) > 0x7fffffffL) return fail(SSP2_EINVAL, "too many attention items");
+  ssp2_engine e;
+  e.d.dim = dim; e.d.heads = heads; e.tokens = tokens; e.dh = d_h;
+  e.opt[SSP2_OPT_ATTN_STREAM] = 2;
+  e.stream = (hipStream_t)hip_stream; e.n_cu = op_cu_count(); e.dev = cur_device();
+  e.qkvbuf = (bf16*)qkv_dev; e.q_cls = (bf16*)q_cls_dev;
+  e.obuf = e.o_cls = (bf16*)out_dev; e.o_ld = ldo;
+  return launch_attn_stream(&e, n, make_rowmap(tokens, n, group), q_cls_dev != nullptr);
 }
 
 // LayerNorm on its own, on caller-owned buffers: launch_ln of a temporary engine (the forward's MAXV / FULL dispatch and its

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 #include "../attn.hip.h"
+#include "../attn_stream.hip.h"
 
 // ------------------------------------------------------------------------------------------------------------------
 // EXPERIMENT (not launched by the engine) - d_h = 64, full attention, TWO-PASS tile: one workgroup of NT waves per (image, head), one 32-query tile per wave.
@@ -206,6 +207,60 @@ int main(int argc, char** argv) {
       printf("calib grid %d: %.3f ticks per dependent v_add_f32, %.3f ns per v_add (wall) -> s_memtime runs at %.3f GHz\n", grid, (double)h / (iters * 100.0),
              ms * 1e6 / (iters * 100.0), (double)h / (ms * 1e6));
     }
+    return 0;
+  }
+  if (argc > 1 && !strcmp(argv[1], "stream")) {
+    // attn_bench stream [n] [heads]: the key-streaming kernel at 197 / 257 / 577 / 785 / 1025 tokens next to the resident kernels the
+    // engine launches at 197 (attn64_persist_kernel<7, 1>) and 257 (attn_fwd_kernel<64, 9>), on n images x heads; median of 9 launches.
+    // Work = 4 T^2 d_h flops per (image, head) (S = QK^T and O = PV); query.key pairs = T^2 per (image, head).
+    hipDeviceProp_t pr; CK(hipGetDeviceProperties(&pr, 0));
+    const int nCU = pr.multiProcessorCount;
+    const int n = argc > 2 ? atoi(argv[2]) : 256, heads = argc > 3 ? atoi(argv[3]) : 12;
+    const int dim = heads * 64, ld = 3 * dim;
+    const size_t max_rows = (size_t)n * 1025;
+    bf16 *qkv, *o;
+    CK(hipMalloc(&qkv, max_rows * ld * 2)); CK(hipMalloc(&o, max_rows * dim * 2));
+    {
+      std::vector<uint16_t> h(max_rows * ld);
+      srand(5);
+      for (auto& v : h) v = f2bf((rand() / (float)RAND_MAX) * 4.f - 2.f);
+      CK(hipMemcpy(qkv, h.data(), h.size() * 2, hipMemcpyHostToDevice));
+    }
+    CK(hipFuncSetAttribute((const void*)attn64_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_STREAM_SMEM));
+    constexpr int psmem = 2 * 2 * 7 * 32 * 128 + 7 * 4096, fsmem9 = 9 * 32 * 256 + 4 * 4096;
+    CK(hipFuncSetAttribute((const void*)attn64_persist_kernel<7, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, psmem));
+    CK(hipFuncSetAttribute((const void*)attn_fwd_kernel<64, 9, false>, hipFuncAttributeMaxDynamicSharedMemorySize, fsmem9));
+    hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
+    const int items = heads * n;
+    auto time = [&](const char* name, int tokens, int which) {
+      const RowMap rm{tokens, 0, 0};
+      std::vector<float> ms;
+      for (int r = 0; r < 10; ++r) {
+        CK(hipEventRecord(a));
+        if (which == 0) {
+          const int qblocks = (tokens + 32 * ATTN_STREAM_QW - 1) / (32 * ATTN_STREAM_QW);
+          hipLaunchKernelGGL(attn64_stream_kernel, dim3(items * qblocks), dim3(64 * (ATTN_STREAM_QW + 1)), ATTN_STREAM_SMEM, 0, qkv, ld, o, dim,
+                             tokens, dim, heads, qblocks, 0.125f, rm);
+        } else if (which == 1) {
+          hipLaunchKernelGGL((attn64_persist_kernel<7, 1>), dim3(std::min(items, nCU)), dim3(512), psmem, 0, qkv, ld, o, dim, tokens, dim, heads, items,
+                             0.125f, rm, 0, 0, (uint8_t*)nullptr, 0, (unsigned int*)nullptr, ATTN_OUT8_SCALE);
+        } else {
+          hipLaunchKernelGGL((attn_fwd_kernel<64, 9, false>), dim3(heads, n), dim3(256), fsmem9, 0, qkv, ld, qkv, (size_t)tokens * ld, ld, o,
+                             (size_t)tokens * dim, dim, tokens, dim, 0.125f, rm);
+        }
+        CK(hipGetLastError());
+        CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
+        float t; CK(hipEventElapsedTime(&t, a, b));
+        if (r) ms.push_back(t);                                   // the first launch warms up
+      }
+      std::sort(ms.begin(), ms.end());
+      const double us = ms[ms.size() / 2] * 1e3, pairs = (double)items * tokens * tokens;
+      printf("%-26s T=%5d  %9.1f us  %7.1f TFLOP/s  %8.3f Tpairs/s  (%d items)\n", name, tokens, us, 4.0 * pairs * 64 / (us * 1e-6) / 1e12,
+             pairs / (us * 1e-6) / 1e12, items);
+    };
+    time("resident persist<7,LIVE>", 197, 1);
+    time("resident one-item<64,9>", 257, 2);
+    for (int t : {197, 257, 577, 785, 1025}) time("stream", t, 0);
     return 0;
   }
   hipDeviceProp_t pr; CK(hipGetDeviceProperties(&pr, 0));

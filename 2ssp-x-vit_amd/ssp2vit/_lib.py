@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(PKG_ROOT, "lib", "libssp2vit.so")
 INCLUDE = os.path.join(os.path.dirname(PKG_ROOT), "include")
 
 SLAB_ALIGN = 128                                        # csrc/common.hip.h kSlabAlign: slabs of the slab layout are padded to a multiple of this many rows
-ABI_VERSION = 6                                         # SSP2_ABI_VERSION of include/ssp2vit.h
+ABI_VERSION = 7                                         # SSP2_ABI_VERSION of include/ssp2vit.h
 
 # every symbol include/ssp2vit.h declares
 SYMBOLS = [
@@ -24,13 +24,16 @@ SYMBOLS = [
     "ssp2_embed", "ssp2_layers", "ssp2_layers_from", "ssp2_layers_prefix", "ssp2_head", "ssp2_tail", "ssp2_tail_slots", "ssp2_tail_group", "ssp2_prune_ffn", "ssp2_drop_attention", "ssp2_d_int", "ssp2_act_l2_accum", "ssp2_profile_begin", "ssp2_profile_end",
     "ssp2_tokens", "ssp2_rows", "ssp2_workspace_bytes", "ssp2_preproc_create", "ssp2_preproc_run", "ssp2_preproc_destroy",
     "ssp2_fp8_calibrate_begin", "ssp2_fp8_calibrate_end", "ssp2_fp8_attn_scale", "ssp2_fp8_set_attn_scale",
+    "ssp2_create_opts", "ssp2_attention_stream_bf16",
 ]
 
 T_KINDS = ["patch_w", "patch_b", "cls", "pos", "ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b",
            "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "lnf_g", "lnf_b", "head_w", "head_b"]
 SCORE_SITE = {"none": 0, "pre_gelu": 1, "post_gelu": 2}
 SCORE_CHAIN = {"fp32": 0, "bf16_ref": 1}
-OPTIONS = {"zigzag": 0, "attn_persist": 1, "ln_fusion": 2, "big_tiles": 3, "fc1_big_tiles": 4, "group256": 5, "patch_lds": 6, "attn_stagger": 7, "fp8_proj": 8, "big_tile_min_rows": 9, "nt_stores": 10, "defer_resid": 11, "attn_live": 12}   # SSP2_OPT_*
+OPTIONS = {"zigzag": 0, "attn_persist": 1, "ln_fusion": 2, "big_tiles": 3, "fc1_big_tiles": 4, "group256": 5, "patch_lds": 6, "attn_stagger": 7, "fp8_proj": 8, "big_tile_min_rows": 9, "nt_stores": 10, "defer_resid": 11, "attn_live": 12, "attn_stream": 13}   # SSP2_OPT_*
+OPT_COUNT = 14                                          # SSP2_OPT_COUNT
+ATTN_STREAM_MAX_TOKENS = 8192                           # SSP2_ATTN_STREAM_MAX_TOKENS
 K_CLASS = {"gemm_fc1": 0, "gemm_fc2": 1, "gemm_qkv": 2, "gemm_proj": 3, "gemm_patch": 4, "gemm_head": 5,
            "attn": 6, "ln": 7, "score_finish": 8, "act_l2": 9, "other": 10}
 
@@ -212,6 +215,7 @@ def load(build_if_missing: bool = True, variant: Optional[str] = None) -> C.CDLL
     lib.ssp2_abi_version.restype = i32
     lib.ssp2_last_error.restype = C.c_char_p
     lib.ssp2_create.argtypes = [C.POINTER(VitDesc), C.POINTER(vp)]
+    lib.ssp2_create_opts.argtypes = [C.POINTER(VitDesc), C.POINTER(i32), C.POINTER(vp)]
     lib.ssp2_destroy.argtypes = [vp]
     lib.ssp2_set_stream.argtypes = [vp, vp]
     lib.ssp2_load_tensor.argtypes = [vp, i32, i32, C.POINTER(C.c_float), C.c_size_t]
@@ -219,6 +223,7 @@ def load(build_if_missing: bool = True, variant: Optional[str] = None) -> C.CDLL
     lib.ssp2_load_tensors_dev.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp), C.POINTER(C.c_size_t)]
     lib.ssp2_linear_bf16.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, vp, i32, i32]
     lib.ssp2_attention_bf16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, C.c_float, vp, i32, i32, i32]
+    lib.ssp2_attention_stream_bf16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32]
     lib.ssp2_layernorm.argtypes = [vp, vp, C.c_size_t, i32, i32, vp, vp, C.c_float, i32, i32, vp, i32, vp, vp, i32]
     lib.ssp2_embed.argtypes = [vp, vp, i32, vp, i32]
     lib.ssp2_rows.argtypes = [vp, i32, i32]

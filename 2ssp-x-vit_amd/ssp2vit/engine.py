@@ -30,15 +30,21 @@ class VitEngine:
         check(rc, self.lib)
 
     def __init__(self, weights: Optional[Dict], device: str | torch.device = "cuda:0", max_images: int = 64, *,
-                 precision: str = "bf16", lib_variant: Optional[str] = None, _twin_of: Optional["VitEngine"] = None,
-                 _d_int: Optional[Sequence[int]] = None):
+                 precision: str = "bf16", lib_variant: Optional[str] = None, attn_stream: Optional[int] = None,
+                 _twin_of: Optional["VitEngine"] = None, _d_int: Optional[Sequence[int]] = None):
         """`lib_variant`: a named build of the library instead of the product one — "lab" carries the opt-in kernel forms the product
-        does not instantiate (options ln_fusion / defer_resid / group256; ssp2vit/_lib.py VARIANT_FLAGS)."""
+        does not instantiate (options ln_fusion / defer_resid / group256; ssp2vit/_lib.py VARIANT_FLAGS).
+        `attn_stream`: SSP2_OPT_ATTN_STREAM in force when the engine is created (None: the environment's SSP2_ATTN_STREAM, default 0).
+        0 = resident attention kernels only (d_h = 64 up to 288 tokens); 1 = longer d_h = 64 sequences (384-pixel /16: 577 tokens,
+        224-pixel /8: 785) on the key-streaming kernel; 2 = every d_h = 64 attention streams (cross-checks).  A twin inherits it."""
         if precision not in ("bf16", "fp8"):
             raise ValueError(f"precision must be 'bf16' or 'fp8', got {precision!r}")
+        if attn_stream is not None and (isinstance(attn_stream, bool) or attn_stream not in (0, 1, 2)):
+            raise ValueError(f"attn_stream must be None, 0, 1 or 2, got {attn_stream!r}")
         self.precision = precision
         if _twin_of is not None:          # same architecture, other FFN widths, weights cloned on the device
             src = _twin_of
+            attn_stream = src.attn_stream
             weights = dict(depth=src.depth, dim=src.dim, classes=src.classes, img=src.img, patch=src.patch, heads=src.heads,
                            eps=src.eps, **{f"fc1_w.{i}": torch.empty(int(d), 0) for i, d in enumerate(_d_int)})
             device = src.device
@@ -65,9 +71,13 @@ class VitEngine:
                        float(weights.get("eps", 1e-6)), self.max_images, arr)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            self._check(self.lib.ssp2_create(C.byref(desc), C.byref(h)))
+            opts = (C.c_int32 * _lib.OPT_COUNT)(*([-1] * _lib.OPT_COUNT))
+            if attn_stream is not None:
+                opts[OPTIONS["attn_stream"]] = int(attn_stream)
+            self._check(self.lib.ssp2_create_opts(C.byref(desc), opts, C.byref(h)))
             self.h = h
             self.tokens = self.lib.ssp2_tokens(self.h)
+            self.attn_stream = self.get_option("attn_stream")
             if _twin_of is None:
                 self._load(weights)
                 if precision == "fp8":
@@ -418,12 +428,17 @@ class VitEngine:
     def attention(self, qkv: torch.Tensor, n: int, tokens: int, heads: int, d_h: int, *, group: int = 0,
                   out: Optional[torch.Tensor] = None, out8: Optional[torch.Tensor] = None, out8_scale: float = 16.0,
                   sat: Optional[torch.Tensor] = None, q_cls: Optional[torch.Tensor] = None, persist: Optional[bool] = None,
-                  live: Optional[bool] = None, rev: int = 0) -> torch.Tensor:
+                  live: Optional[bool] = None, rev: int = 0, stream: bool = False) -> torch.Tensor:
         """Multi-head attention of the forward on its own (ssp2_attention_bf16), on caller-owned buffers: qkv bf16
         [>= rows, 3 * heads * d_h] densely packed, with rows = ssp2_rows(n, group).  Writes out (bf16 [>= rows, ldo], allocated when None) or,
         with out8 (uint8 [>= rows, ldo8]), the fp8 mode's e4m3(o * out8_scale) bytes, counting clipping waves into sat (int32
         [1]).  q_cls (bf16 [>= n, dim], densely packed): the CLS-only form, out [>= n, ldo].  persist / live override SSP2_OPT_ATTN_PERSIST /
-        SSP2_OPT_ATTN_LIVE (None: on); rev: walk direction of the persistent kernels.  Returns the tensor written."""
+        SSP2_OPT_ATTN_LIVE (None: on); rev: walk direction of the persistent kernels.  stream=True: the key-streaming kernel instead
+        (ssp2_attention_stream_bf16, see attention_stream; bf16 output only).  Returns the tensor written."""
+        if stream:
+            if out8 is not None or sat is not None or persist is not None or live is not None:
+                raise ValueError("the key-streaming attention writes bf16 only and has no persist / live switches")
+            return self.attention_stream(qkv, n, tokens, heads, d_h, group=group, out=out, q_cls=q_cls)
         dim = heads * d_h
         named = (("qkv", qkv, torch.bfloat16), ("out", out, torch.bfloat16), ("out8", out8, torch.uint8), ("q_cls", q_cls, torch.bfloat16))
         for name, t, dt in named:
@@ -447,6 +462,27 @@ class VitEngine:
                                            group, _ptr(q_cls), _ptr(out), out.stride(0) if out is not None else 0, _ptr(out8),
                                            out8.stride(0) if out8 is not None else 0, float(out8_scale), _ptr(sat), flag[persist], flag[live], int(rev)))
         return out8 if out8 is not None else out
+
+    def attention_stream(self, qkv: torch.Tensor, n: int, tokens: int, heads: int, d_h: int, *, group: int = 0,
+                         out: Optional[torch.Tensor] = None, q_cls: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The key-streaming attention on its own (ssp2_attention_stream_bf16): the layouts of `attention`, d_h = 64, 1..8192 tokens,
+        bf16 output only."""
+        dim = heads * d_h
+        for name, t in (("qkv", qkv), ("out", out), ("q_cls", q_cls)):
+            if t is not None and (t.device.type != "cuda" or t.dim() != 2 or t.dtype != torch.bfloat16 or t.stride(1) != 1 or t.stride(0) < t.shape[1]):
+                raise ValueError(f"{name} must be a row-major 2-D bf16 device tensor")
+        need = n if q_cls is not None else ssp2_rows(n, tokens, group)
+        if qkv.shape[1] != 3 * dim or qkv.stride(0) != 3 * dim or (q_cls is not None and (q_cls.shape[1] != dim or q_cls.stride(0) != dim)):
+            raise ValueError(f"qkv must be [rows, {3 * dim}] and q_cls [n, {dim}], densely packed (the kernels' row strides)")
+        if qkv.shape[0] < ssp2_rows(n, tokens, group) or (q_cls is not None and q_cls.shape[0] < n):
+            raise ValueError(f"qkv [{tuple(qkv.shape)}] / q_cls too small for n={n} tokens={tokens} heads={heads} d_h={d_h} group={group}")
+        if out is None:
+            out = torch.empty(need, dim, dtype=torch.bfloat16, device=qkv.device)
+        if out.shape[0] < need or out.shape[1] < dim:
+            raise ValueError(f"output [{tuple(out.shape)}] smaller than [{need}, {dim}]")
+        self._check(self.lib.ssp2_attention_stream_bf16(C.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream), _ptr(qkv), n, tokens,
+                                                        heads, d_h, group, _ptr(q_cls), _ptr(out), out.stride(0)))
+        return out
 
     def layernorm(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, *, rows: Optional[int] = None,
                   in_stride: Optional[int] = None, gather: Optional[Tuple[int, int]] = None, out: Optional[torch.Tensor] = None,

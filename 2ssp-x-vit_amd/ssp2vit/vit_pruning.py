@@ -118,15 +118,33 @@ def _fingerprint(model) -> Tuple:
 # opt-in, "fp8" (BASELINE configs[4]: QKV / fc1 / fc2 / out-projection of launches with >= 4096 token rows on e4m3 MFMA operands — a
 # tolerance mode).  SSP2_PRECISION sets the default; the CLI's --precision sets this variable.
 DEFAULT_PRECISION = os.environ.get("SSP2_PRECISION", "bf16")
+# SSP2_OPT_ATTN_STREAM of the engines built for live modules: None = the environment (SSP2_ATTN_STREAM); the CLI's --long-sequences sets 1
+DEFAULT_ATTN_STREAM: Optional[int] = None
 _FP8_SCALES: Dict[int, List[float]] = {}          # id(model) -> calibrated attention hand-off scales (calibrate_fp8), re-applied when an engine is rebuilt
 
 
-def engine_for(model, device="cuda", max_images: int = 64, precision: Optional[str] = None):
-    """Build (or reuse) the HIP engine holding `model`'s current weights.  Raises without a GPU."""
+def attn_stream_setting(attn_stream: Optional[int] = None) -> int:
+    """The SSP2_OPT_ATTN_STREAM an engine built now gets: the argument, else DEFAULT_ATTN_STREAM (the CLI's --long-sequences), else the
+    environment's SSP2_ATTN_STREAM (what ssp2_create reads), else 0."""
+    if attn_stream is None:
+        attn_stream = DEFAULT_ATTN_STREAM
+    if attn_stream is None:
+        v = os.environ.get("SSP2_ATTN_STREAM", "")
+        try:
+            attn_stream = max(0, min(2, int(v))) if v else 0
+        except ValueError:
+            attn_stream = 0
+    return int(attn_stream)
+
+
+def engine_for(model, device="cuda", max_images: int = 64, precision: Optional[str] = None, attn_stream: Optional[int] = None):
+    """Build (or reuse) the HIP engine holding `model`'s current weights.  Raises without a GPU.  `attn_stream`: see
+    VitEngine (None: attn_stream_setting()); the cache and the pool are keyed on it as well as on the geometry."""
     from .engine import VitEngine
     precision = precision or DEFAULT_PRECISION
+    attn_stream = attn_stream_setting(attn_stream)
     key = id(model)
-    fp = _fingerprint(model) + (precision,)
+    fp = _fingerprint(model) + (precision, attn_stream)
     hit = _ENGINES.get(key)
     if hit is not None and hit[0] == fp and hit[1].max_images >= max_images:
         return hit[1]
@@ -139,11 +157,11 @@ def engine_for(model, device="cuda", max_images: int = 64, precision: Optional[s
     dev = torch.device(device if str(device) != "cuda" else f"cuda:{torch.cuda.current_device()}") \
         if torch.cuda.is_available() else torch.device(device)
     flat = _weights.from_module(model)
-    eng = _from_pool(flat, dev, max(int(max_images), 1), precision)
+    eng = _from_pool(flat, dev, max(int(max_images), 1), precision, attn_stream)
     while len(_POOL) > ENGINE_POOL_MAX:
         _POOL.pop(0).close()
     if eng is None:
-        eng = VitEngine(flat, device=dev, max_images=max(int(max_images), 1), precision=precision)
+        eng = VitEngine(flat, device=dev, max_images=max(int(max_images), 1), precision=precision, attn_stream=attn_stream)
     eng.layout = _weights.detect_layout(model)
     if precision == "fp8" and key in _FP8_SCALES and len(_FP8_SCALES[key]) == eng.depth:
         for l, sc in enumerate(_FP8_SCALES[key]):
@@ -170,12 +188,13 @@ ENGINE_POOL_MAX = int(os.environ.get("SSP2_ENGINE_POOL", "1"))
 _POOL: List[Any] = []
 
 
-def _from_pool(flat, dev, max_images: int, precision: str):
+def _from_pool(flat, dev, max_images: int, precision: str, attn_stream: int = 0):
     if precision != "bf16":
         return None
     for i, e in enumerate(_POOL):
         try:
             same = (str(e.device) == str(dev) and e.precision == precision and e.max_images >= max_images and e.lib_variant is None
+                    and getattr(e, "attn_stream", 0) == attn_stream
                     and (e.img, e.patch, e.dim, e.heads, e.depth, e.classes) == tuple(int(flat[k]) for k in ("img", "patch", "dim", "heads", "depth", "classes"))
                     and abs(e.eps - float(flat.get("eps", 1e-6))) < 1e-15
                     and [int(d) for d in e.d_int] == [int(flat[f"fc1_w.{l}"].shape[0]) for l in range(e.depth)])

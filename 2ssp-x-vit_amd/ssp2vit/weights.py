@@ -47,6 +47,16 @@ VIT_CONFIGS = {
     "vit_base_patch16_160_d2": (160, 16, 768, 12, 3072, 2),
     "vit_base_patch16_208_d2": (208, 16, 768, 12, 3072, 2),
     "vit_base_patch16_240_d2": (240, 16, 768, 12, 3072, 2),
+    # sequences over 288 tokens (the key-streaming attention: SSP2_ATTN_STREAM=1 / VitEngine(attn_stream=1) / --long-sequences):
+    # the reference's SRP models at 384 pixels (577 tokens) and test cuts of them, /8 at 224 (785 tokens), /16 at 512 (1025 tokens)
+    "vit_tiny_patch16_384": (384, 16, 192, 3, 768, 12),
+    "vit_small_patch16_384": (384, 16, 384, 6, 1536, 12),
+    "vit_base_patch16_384": (384, 16, 768, 12, 3072, 12),
+    "vit_large_patch16_384": (384, 16, 1024, 16, 4096, 24),
+    "vit_small_patch16_384_d3": (384, 16, 384, 6, 1536, 3),
+    "vit_base_patch16_384_d2": (384, 16, 768, 12, 3072, 2),
+    "vit_small_patch8_224_d2": (224, 8, 384, 6, 1536, 2),
+    "vit_tiny_patch16_512_d2": (512, 16, 192, 3, 768, 2),
 }
 
 

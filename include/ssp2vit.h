@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SSP2_ABI_VERSION 6
+#define SSP2_ABI_VERSION 7
 
 enum {
   SSP2_OK = 0,
@@ -61,7 +61,9 @@ typedef struct {
   int32_t dim;          /* hidden size, multiple of 64                             */
   int32_t heads;        /* dim/heads in {16, 64, 80}; tokens = (img/patch)^2 + 1 must fall into an instantiated key-tile count:
                          * d_h 64: up to 288 tokens (ViT-Ti/S/B/L at /16 and /32 up to 256 pixels; ViT-L/14); d_h 80: 257..288 (ViT-H/14);
-                         * d_h 16: up to 32 — anything else is refused by ssp2_create with SSP2_EINVAL */
+                         * d_h 16: up to 32 — anything else is refused by ssp2_create with SSP2_EINVAL.  With SSP2_OPT_ATTN_STREAM >= 1
+                         * (environment SSP2_ATTN_STREAM, or ssp2_create_opts) d_h 64 also takes 289..SSP2_ATTN_STREAM_MAX_TOKENS tokens
+                         * (ViT-Ti/S/B/L at 384 pixels: 577; /8 at 224: 785) on the key-streaming kernel */
   int32_t depth;        /* encoder blocks L                                        */
   int32_t classes;
   float   ln_eps;       /* 1e-6 timm, 1e-12 HF                                     */
@@ -75,6 +77,10 @@ const char* ssp2_last_error(void);
 /* Replaces: model construction + `.to(device)` of the third-party ViT the reference calls
  * (src/vit_pruning.py:180, :354).  Allocates bf16 weight storage and the activation workspace. */
 int ssp2_create(const ssp2_vit_desc* desc, ssp2_handle* out);
+/* ssp2_create with option overrides that are in force BEFORE the geometry is validated: opt[SSP2_OPT_COUNT], each entry -1 (the
+ * environment's default, as ssp2_create) or the option's value (SSP2_OPT_ATTN_STREAM = 1 lets a > 288-token d_h 64 model be created
+ * without touching the environment).  opt == NULL is ssp2_create. */
+int ssp2_create_opts(const ssp2_vit_desc* desc, const int32_t* opt, ssp2_handle* out);
 int ssp2_destroy(ssp2_handle h);
 int ssp2_set_stream(ssp2_handle h, void* hip_stream);
 /* Cap the grids of the handle's persistent kernels (large-tile GEMMs, d_h = 64 attention) at n_cu workgroups (<= 0 or
@@ -103,10 +109,17 @@ int ssp2_set_cu_limit(ssp2_handle h, int n_cu);
  *                                                   tile's main loop (bf16 operands, dim a multiple of 256); same bits as the direct epilogue
  *   SSP2_OPT_ATTN_LIVE      1  SSP2_ATTN_LIVE       persistent attention at 197 / 257 tokens on the instantiation that knows at compile time that the
  *                                                   last key tile holds ONE live register group (5 / 1 valid keys): the padding's maxima,
- *                                                   exponentials, sums and P V half are not emitted; 0 = the general instantiation */
+ *                                                   exponentials, sums and P V half are not emitted; 0 = the general instantiation
+ *   SSP2_OPT_ATTN_STREAM    0  SSP2_ATTN_STREAM     d_h = 64 attention on the key-streaming kernel (online softmax, csrc/attn_stream.hip.h):
+ *                                                   0 = the resident kernels only (a longer sequence is refused at creation); 1 = sequences
+ *                                                   over 288 tokens stream, shorter ones keep the resident kernels bit for bit; 2 = every
+ *                                                   d_h = 64 attention streams (cross-checks; within tolerance of the resident kernels, not
+ *                                                   bit-identical).  An engine whose geometry needs it refuses 0 (SSP2_ESTATE); a streaming
+ *                                                   engine refuses fp8 (ssp2_set_precision: SSP2_ESTATE) */
 enum { SSP2_OPT_ZIGZAG = 0, SSP2_OPT_ATTN_PERSIST, SSP2_OPT_LN_FUSION, SSP2_OPT_BIG_TILES, SSP2_OPT_FC1_BIG_TILES, SSP2_OPT_GROUP256,
        SSP2_OPT_PATCH_LDS, SSP2_OPT_ATTN_STAGGER, SSP2_OPT_FP8_PROJ, SSP2_OPT_BIG_TILE_MIN_ROWS, SSP2_OPT_NT_STORES,
-       SSP2_OPT_DEFER_RESID, SSP2_OPT_ATTN_LIVE, SSP2_OPT_COUNT };
+       SSP2_OPT_DEFER_RESID, SSP2_OPT_ATTN_LIVE, SSP2_OPT_ATTN_STREAM, SSP2_OPT_COUNT };
+#define SSP2_ATTN_STREAM_MAX_TOKENS 8192   /* longest sequence of the key-streaming attention */
 int ssp2_set_option(ssp2_handle h, int option, int value);
 int ssp2_get_option(ssp2_handle h, int option);                             /* >= 0, or SSP2_EINVAL */
 
@@ -275,6 +288,13 @@ int ssp2_linear_bf16(void* hip_stream, int epilogue, const uint16_t* a_dev, int 
 int ssp2_attention_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
                         const uint16_t* q_cls_dev, uint16_t* out_dev, int ldo, uint8_t* out8_dev, int ldo8, float out8_scale,
                         unsigned int* sat_dev, int persist, int live, int rev);
+/* The key-streaming attention on its own (the kernel SSP2_OPT_ATTN_STREAM routes to), same layouts and arguments as
+ * ssp2_attention_bf16 without the e4m3 output: d_h = 64, 1 <= tokens <= SSP2_ATTN_STREAM_MAX_TOKENS.  Online softmax over
+ * 128-key stages: fp32 scores, running max m and sum, P = bf16(exp2(fma(s, c2, -m c2))) for P V, O and the sum rescaled by
+ * exp2((m_old - m) c2) when the max grows, one bf16 rounding of the output.  The CLS-only form (q_cls_dev != NULL) keeps P in
+ * fp32.  Every argument is checked before the device is touched. */
+int ssp2_attention_stream_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
+                               const uint16_t* q_cls_dev, uint16_t* out_dev, int ldo);
 
 /* LayerNorm over the last dim on its own, on caller-owned device buffers: the forward's launch (one instantiation per 256-wide
  * step of D, the unpredicated form where D = 256 * MAXV, the reverse walk from 4096 rows on when rev = 1).
