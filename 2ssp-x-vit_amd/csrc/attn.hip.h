@@ -113,14 +113,17 @@ __device__ __forceinline__ float softmax_tile(f32x16 (&sacc)[NT], const int toke
   return sum;
 }
 
-// CLS_ONLY (evaluation tail): only query 0 of every image is needed.  q then comes from a compact [n, dim] buffer
-// (q_img_stride = dim, q_ld = 0: the whole 32-query tile reads the CLS row) and only row 0 is stored, into a compact
-// [n, dim] output.  The arithmetic for query 0 is the same instruction sequence as in the full kernel, so the tail
-// is bit-identical to running the whole block.
+// CLS_ONLY (evaluation tail): only the nq prefix queries of every image are needed (nq = 1: CLS; 2: CLS and the distillation
+// token of a distilled DeiT).  q then comes from a compact prefix-major [nq][n, dim] buffer (q_img_stride = dim, q_ld = the
+// stride from prefix row 0 to row 1, n * dim): lane row r < nq of the 32-query tile reads prefix query r, the rows behind it
+// repeat query nq - 1, and only rows < nq are stored, into the compact prefix-major output (o_img_stride = ldo of a row, ldo =
+// the prefix stride).  The arithmetic of query r is the same instruction sequence as in the full kernel, so the tail is
+// bit-identical to running the whole block.
 template <int DH, int NT, bool CLS_ONLY = false>
 __global__ __launch_bounds__(256, (DH == 64 ? 2 : 1)) void attn_fwd_kernel(const bf16* __restrict__ qkv, int ld, const bf16* __restrict__ qsrc,
                                                       size_t q_img_stride, int q_ld, bf16* __restrict__ out,
-                                                      size_t o_img_stride, int ldo, int tokens, int dim, float scale, RowMap rm) {
+                                                      size_t o_img_stride, int ldo, int tokens, int dim, float scale, RowMap rm,
+                                                      int nq = 1) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int DT = (DH + 31) / 32;     // 32-row tiles of the O^T output (d_h padded up)
   constexpr int KS = DH / 16;            // k-steps of the QK^T product
@@ -152,9 +155,10 @@ __global__ __launch_bounds__(256, (DH == 64 ? 2 : 1)) void attn_fwd_kernel(const
   // Q fragments of the wave's first query tile go out first; the next tile's are fetched behind the current tile's
   // QK^T (software pipeline: no query load is ever waited for at the top of a tile)
   const bf16* qbase = (CLS_ONLY ? qsrc + (size_t)img * q_img_stride : qsrc + img_row * ld) + head * DH;
+  const int qrows = CLS_ONLY ? nq : tokens;     // query rows that exist: rows past them repeat the last one
   auto load_q = [&](int qt, bf16x8 (&dst)[KS]) {
     const int q = qt * 32 + l31;
-    const int qc = q < tokens ? q : tokens - 1;
+    const int qc = q < qrows ? q : qrows - 1;
     const bf16* qp = qbase + (size_t)qc * q_ld + 8 * lh;
 #pragma unroll
     for (int s = 0; s < KS; ++s) dst[s] = *(const bf16x8*)(qp + 16 * s);
@@ -352,7 +356,7 @@ __global__ __launch_bounds__(256, (DH == 64 ? 2 : 1)) void attn_fwd_kernel(const
       }
     } else
     // lane <-> query row, 4 consecutive d_h per 8-byte store
-    if (CLS_ONLY ? (q == 0) : (q < tokens)) {
+    if (q < qrows) {
       bf16* op = (CLS_ONLY ? out + (size_t)img * o_img_stride : out + img_row * ldo) + (size_t)q * ldo + head * DH;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt)

@@ -20,8 +20,8 @@
 // The output goes through a wave-private [32 queries][128 B] LDS tile (placed in the ring buffer the last stage does not use) as
 // whole 128-byte row segments.
 //
-// CLS-only form (attn64_stream_cls_kernel, the evaluation tail): one query per (image, head) against every key.  One wave per item,
-// four items per workgroup: lane <-> key for the scores (chunks of 64 keys, online max / sum as above, f32 probabilities), then
+// CLS-only form (attn64_stream_cls_kernel<P>, the evaluation tail): P = 1 or 2 prefix queries per (image, head) against every key.  One
+// wave per item, four items per workgroup: lane <-> key for the scores (chunks of 64 keys, online max / sum as above, f32 probabilities), then
 // lane <-> d_h for P V (the chunk's probabilities broadcast by ds_bpermute).  q from the compact [n, q_img_stride] buffer, output to
 // the compact [n, o_img_stride] buffer, as attn_fwd_kernel<64, NT, true>.
 //
@@ -220,55 +220,76 @@ __global__ __launch_bounds__(64 * (ATTN_STREAM_QW + 1), 2) void attn64_stream_ke
   }
 }
 
-// CLS-only form: wave = one (image, head) item, 4 items per 256-thread workgroup (no LDS, no barrier)
+// CLS-only form: wave = one (image, head) item, 4 items per 256-thread workgroup (no LDS, no barrier).  P prefix queries per item
+// (P = 1: CLS; P = 2: CLS and the distillation token, q and out prefix-major with the strides q_pstride / o_pstride): the P queries
+// share every key and value load and keep P online-softmax states; for P = 1 the instruction sequence is the single-query one.
+template <int P>
 __global__ __launch_bounds__(256) void attn64_stream_cls_kernel(const bf16* __restrict__ qkv, int ld, const bf16* __restrict__ qsrc, size_t q_img_stride,
                                                                 bf16* __restrict__ out, size_t o_img_stride, int tokens, int dim, int heads, int n_items,
-                                                                float scale, RowMap rm) {
+                                                                float scale, RowMap rm, size_t q_pstride = 0, size_t o_pstride = 0) {
   const int lane = threadIdx.x & 63;
   const int item = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
   if (item >= n_items) return;                                  // wave-uniform
   const int img = item / heads, head = item - img * heads;
   const bf16* const base = qkv + (size_t)row_of(rm, img) * ld + head * 64;
   const float c2 = scale * 1.44269504088896340736f;
-  float q[64];
-  {
-    const bf16* qp = qsrc + (size_t)img * q_img_stride + head * 64;
+  float q[P][64];
+#pragma unroll
+  for (int t = 0; t < P; ++t) {
+    const bf16* qp = qsrc + (size_t)t * q_pstride + (size_t)img * q_img_stride + head * 64;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       const bf16x8 v = *(const bf16x8*)(qp + 8 * c);
 #pragma unroll
-      for (int jj = 0; jj < 8; ++jj) q[8 * c + jj] = (float)v[jj];
+      for (int jj = 0; jj < 8; ++jj) q[t][8 * c + jj] = (float)v[jj];
     }
   }
-  float m_run = -INFINITY, l_lane = 0.f, o = 0.f;               // o: output column d = lane
+  float m_run[P], l_lane[P], o[P];                              // o: output column d = lane
+#pragma unroll
+  for (int t = 0; t < P; ++t) { m_run[t] = -INFINITY; l_lane[t] = 0.f; o[t] = 0.f; }
   for (int k0 = 0; k0 < tokens; k0 += 64) {
     const int key = k0 + lane;
     const int kc = key < tokens ? key : tokens - 1;
     const bf16* kp = base + (size_t)kc * ld + dim;
-    float s = 0.f;
+    float s[P];
+#pragma unroll
+    for (int t = 0; t < P; ++t) s[t] = 0.f;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       const bf16x8 v = *(const bf16x8*)(kp + 8 * c);
 #pragma unroll
-      for (int jj = 0; jj < 8; ++jj) s = fmaf((float)v[jj], q[8 * c + jj], s);
-    }
-    if (key >= tokens) s = -INFINITY;
-    float mx = s;
+      for (int jj = 0; jj < 8; ++jj)
 #pragma unroll
-    for (int w = 32; w >= 1; w >>= 1) mx = fmaxf(mx, __shfl_xor(mx, w));
-    const float m_new = fmaxf(m_run, mx);
-    const float mc = -m_new * c2;
-    const float alpha = __builtin_amdgcn_exp2f(fmaf(m_run, c2, mc));
-    m_run = m_new;
-    const float p = __builtin_amdgcn_exp2f(fmaf(s, c2, mc));
-    l_lane = fmaf(l_lane, alpha, p);
-    o *= alpha;
+        for (int t = 0; t < P; ++t) s[t] = fmaf((float)v[jj], q[t][8 * c + jj], s[t]);
+    }
+    float p[P];
+#pragma unroll
+    for (int t = 0; t < P; ++t) {
+      if (key >= tokens) s[t] = -INFINITY;
+      float mx = s[t];
+#pragma unroll
+      for (int w = 32; w >= 1; w >>= 1) mx = fmaxf(mx, __shfl_xor(mx, w));
+      const float m_new = fmaxf(m_run[t], mx);
+      const float mc = -m_new * c2;
+      const float alpha = __builtin_amdgcn_exp2f(fmaf(m_run[t], c2, mc));
+      m_run[t] = m_new;
+      p[t] = __builtin_amdgcn_exp2f(fmaf(s[t], c2, mc));
+      l_lane[t] = fmaf(l_lane[t], alpha, p[t]);
+      o[t] *= alpha;
+    }
     const int kn = tokens - k0 < 64 ? tokens - k0 : 64;        // valid keys of the chunk (wave-uniform)
     const bf16* vp = base + (size_t)k0 * ld + 2 * dim + lane;
-    for (int kk = 0; kk < kn; ++kk) o = fmaf(__shfl(p, kk), (float)vp[(size_t)kk * ld], o);
-  }
-  float l = l_lane;
+    for (int kk = 0; kk < kn; ++kk) {
+      const float v = (float)vp[(size_t)kk * ld];
 #pragma unroll
-  for (int w = 32; w >= 1; w >>= 1) l += __shfl_xor(l, w);
-  out[(size_t)img * o_img_stride + head * 64 + lane] = (bf16)(o / l);
+      for (int t = 0; t < P; ++t) o[t] = fmaf(__shfl(p[t], kk), v, o[t]);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < P; ++t) {
+    float l = l_lane[t];
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) l += __shfl_xor(l, w);
+    out[(size_t)t * o_pstride + (size_t)img * o_img_stride + head * 64 + lane] = (bf16)(o[t] / l);
+  }
 }

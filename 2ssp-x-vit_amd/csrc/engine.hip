@@ -91,6 +91,9 @@ struct ssp2_engine {
   ssp2_vit_desc d{};
   std::vector<int32_t> d_int;
   int tokens = 0, patches = 0, side = 0, dh = 0;
+  // token layout (ssp2_create_ext): prefix tokens in front of the patches (1: CLS; 2: CLS + distillation token) and whether the
+  // logits average the CLS head with a distillation head on row 1 (tail_rows = rows the evaluation tail carries: 2 with it, else 1)
+  int prefix = 1, dist_head = 0, tail_rows = 1;
   int kpe = 0, kpe_pad = 0, ld_int_max = 0;
   long rows_cap = 0;        // token-matrix rows the workspace is sized for
   hipStream_t stream = nullptr;
@@ -107,15 +110,16 @@ struct ssp2_engine {
   char* arena_cur[2] = {nullptr, nullptr};
   size_t ws_bytes = 0, weight_bytes = 0;
 
-  Mat patch, head;
-  float *cls = nullptr, *pos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr;
+  Mat patch, head, head_dist;
+  float *cls = nullptr, *pos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr, *dist = nullptr;
   bool misc_set[4] = {false, false, false, false};
+  bool dist_set = false;
   std::vector<Layer> layers;
 
   // workspace (sized for max_images)
   bf16 *a_pe = nullptr, *hbuf = nullptr, *qkvbuf = nullptr, *obuf = nullptr, *actbuf = nullptr, *cls_h = nullptr;
   bf16* prebuf = nullptr;   // pre-GELU copy, only for models with < 128 tokens (unfused scoring)
-  // evaluation tail (last block on the CLS rows only)
+  // evaluation tail (last block on the prefix rows only: tail_rows per image, prefix-major [tail_rows][n][...])
   float* x_cls = nullptr;
   bf16 *q_cls = nullptr, *o_cls = nullptr, *h_cls = nullptr, *act_cls = nullptr;
   float *slab = nullptr, *norms = nullptr, *logits = nullptr;
@@ -375,7 +379,7 @@ static int launch_attn_t(ssp2_engine* e, int n, RowMap rm, uint8_t* out8 = nullp
   }
   const int D = e->d.dim, ld = 3 * D, ldo = e->o_ld > 0 ? e->o_ld : D;
   // algorithmic work of a full attention: S = QK^T and O = PV, 2 * N * N * d_h flops each per (image, head); q, k, v read, o written
-  const double qn = CLS ? 1.0 : (double)e->tokens;
+  const double qn = CLS ? (double)e->tail_rows : (double)e->tokens;
   ProfScope ps(e, SSP2_K_ATTN, 4.0 * qn * e->tokens * DH * e->d.heads * n, 2.0 * n * D * (2.0 * e->tokens + 2.0 * qn));
   if constexpr (DH == 64 && !CLS && NT >= 4 && NT <= 7) {
     // persistent producer / consumer form (attn.hip.h); SSP2_OPT_ATTN_PERSIST = 0 keeps the one-item-per-workgroup kernel
@@ -436,9 +440,9 @@ static int launch_attn_t(ssp2_engine* e, int n, RowMap rm, uint8_t* out8 = nullp
     }
   }
   if (out8) return fail(SSP2_ESTATE, "e4m3 attention output needs a persistent attention kernel (d_h = 64 / 80, SSP2_OPT_ATTN_PERSIST)");
-  if (CLS)   // q from the compact CLS projection, only row 0 kept, compact [n, D] output
+  if (CLS)   // q from the compact prefix-major [tail_rows][n, D] projection, rows < tail_rows kept, output in the same order
     hipLaunchKernelGGL((attn_fwd_kernel<DH, NT, true>), dim3(e->d.heads, n), dim3(256), smem, e->stream, e->qkvbuf, ld, e->q_cls,
-                       (size_t)D, 0, e->o_cls, (size_t)ldo, ldo, e->tokens, D, 1.0f / sqrtf((float)DH), rm);
+                       (size_t)D, n * D, e->o_cls, (size_t)ldo, n * ldo, e->tokens, D, 1.0f / sqrtf((float)DH), rm, e->tail_rows);
   else
     hipLaunchKernelGGL((attn_fwd_kernel<DH, NT, false>), dim3(e->d.heads, n), dim3(256), smem, e->stream, e->qkvbuf, ld, e->qkvbuf,
                        (size_t)e->tokens * ld, ld, e->obuf, (size_t)e->tokens * ldo, ldo, e->tokens, D, 1.0f / sqrtf((float)DH), rm);
@@ -471,14 +475,18 @@ static bool attn_supported(int dh, int tokens, int stream = 0) {
 // the key-streaming kernels (attn_stream.hip.h): full attention over the slab / dense rows, or the CLS-only tail
 static int launch_attn_stream(ssp2_engine* e, int n, RowMap rm, bool cls_only) {
   const int D = e->d.dim, ld = 3 * D, ldo = e->o_ld > 0 ? e->o_ld : D, T = e->tokens;
-  const double qn = cls_only ? 1.0 : (double)T;
+  const double qn = cls_only ? (double)e->tail_rows : (double)T;
   ProfScope ps(e, SSP2_K_ATTN, 4.0 * qn * T * 64 * e->d.heads * n, 2.0 * n * D * (2.0 * T + 2.0 * qn));
   const long items = (long)e->d.heads * n;
   const float scale = 1.0f / sqrtf(64.0f);
   if (cls_only) {
     if ((items + 3) / 4 > 0x7fffffffL) return fail(SSP2_EINVAL, "too many attention items");
-    hipLaunchKernelGGL(attn64_stream_cls_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, e->stream, e->qkvbuf, ld, e->q_cls, (size_t)D,
-                       e->o_cls, (size_t)ldo, T, D, e->d.heads, (int)items, scale, rm);
+    if (e->tail_rows == 2)   // CLS and DIST queries in one wave: shared key / value loads, two online-softmax states
+      hipLaunchKernelGGL(attn64_stream_cls_kernel<2>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, e->stream, e->qkvbuf, ld, e->q_cls, (size_t)D,
+                         e->o_cls, (size_t)ldo, T, D, e->d.heads, (int)items, scale, rm, (size_t)n * D, (size_t)n * ldo);
+    else
+      hipLaunchKernelGGL(attn64_stream_cls_kernel<1>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, e->stream, e->qkvbuf, ld, e->q_cls, (size_t)D,
+                         e->o_cls, (size_t)ldo, T, D, e->d.heads, (int)items, scale, rm);
   } else {
     const int qblocks = (T + 32 * ATTN_STREAM_QW - 1) / (32 * ATTN_STREAM_QW);
     if (items * qblocks > 0x7fffffffL) return fail(SSP2_EINVAL, "too many attention items");
@@ -526,10 +534,16 @@ extern "C" {
 int ssp2_abi_version(void) { return SSP2_ABI_VERSION; }
 const char* ssp2_last_error(void) { return g_err.c_str(); }
 
-int ssp2_create(const ssp2_vit_desc* desc, ssp2_handle* out) { return ssp2_create_opts(desc, nullptr, out); }
+int ssp2_create(const ssp2_vit_desc* desc, ssp2_handle* out) { return ssp2_create_ext(desc, nullptr, nullptr, out); }
 
-int ssp2_create_opts(const ssp2_vit_desc* desc, const int32_t* opt, ssp2_handle* out) {
+int ssp2_create_opts(const ssp2_vit_desc* desc, const int32_t* opt, ssp2_handle* out) { return ssp2_create_ext(desc, opt, nullptr, out); }
+
+int ssp2_create_ext(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_vit_ext* ext, ssp2_handle* out) {
   if (!desc || !out || !desc->d_int) return fail(SSP2_EINVAL, "null argument");
+  const int prefix = ext ? ext->prefix_tokens : 1, dist_head = ext ? ext->dist_head : 0;
+  if (prefix < 1 || prefix > 2) return fail(SSP2_EINVAL, "prefix_tokens %d: 1 (CLS) or 2 (CLS + distillation token)", prefix);
+  if (dist_head < 0 || dist_head > 1) return fail(SSP2_EINVAL, "dist_head %d: 0 (CLS head) or 1 (CLS and distillation heads averaged)", dist_head);
+  if (dist_head && prefix != 2) return fail(SSP2_EINVAL, "dist_head = 1 reads the distillation token: it needs prefix_tokens = 2 (got %d)", prefix);
   if (opt) {
     for (int i = 0; i < SSP2_OPT_COUNT; ++i)
       if (opt[i] < -1) return fail(SSP2_EINVAL, "option %d: override %d (-1 = environment default)", i, opt[i]);
@@ -596,7 +610,8 @@ int ssp2_create_opts(const ssp2_vit_desc* desc, const int32_t* opt, ssp2_handle*
   e->d.d_int = e->d_int.data();
   e->side = d.img / d.patch;
   e->patches = e->side * e->side;
-  e->tokens = e->patches + 1;
+  e->prefix = prefix; e->dist_head = dist_head; e->tail_rows = dist_head ? 2 : 1;
+  e->tokens = e->patches + prefix;
   e->dh = d.dim / d.heads;
   e->kpe = 3 * d.patch * d.patch;
   e->kpe_pad = ceil_to(e->kpe, GEMM_BK);
@@ -620,7 +635,9 @@ int ssp2_create_opts(const ssp2_vit_desc* desc, const int32_t* opt, ssp2_handle*
   auto alloc_all = [&]() -> int {
   TRYA(mat_alloc(e, e->patch, d.dim, e->kpe));
   TRYA(mat_alloc(e, e->head, d.classes, d.dim));
+  if (e->dist_head) TRYA(mat_alloc(e, e->head_dist, d.classes, d.dim));
   TRYA(dalloc(e, &e->cls, d.dim, false));
+  if (e->prefix == 2) TRYA(dalloc(e, &e->dist, d.dim, false));
   TRYA(dalloc(e, &e->pos, (size_t)e->tokens * d.dim, false));
   TRYA(dalloc(e, &e->lnf_g, d.dim, false));
   TRYA(dalloc(e, &e->lnf_b, d.dim, false));
@@ -650,13 +667,15 @@ int ssp2_create_opts(const ssp2_vit_desc* desc, const int32_t* opt, ssp2_handle*
   if (e->tokens < GEMM_BM) TRYA(dalloc(e, &e->prebuf, M * e->ld_int_max, true, false));
   TRYA(dalloc(e, &e->slab, tiles_m * 2 * e->ld_int_max, true));
   TRYA(dalloc(e, &e->norms, (size_t)2 * d.max_images * e->ld_int_max, true));   // [2 token halves][n][ld] for the standalone L2 kernel
-  TRYA(dalloc(e, &e->cls_h, (size_t)d.max_images * d.dim, true));
-  TRYA(dalloc(e, &e->x_cls, (size_t)d.max_images * d.dim, true));
-  TRYA(dalloc(e, &e->q_cls, (size_t)d.max_images * d.dim, true));
-  TRYA(dalloc(e, &e->o_cls, (size_t)d.max_images * d.dim, true));
-  TRYA(dalloc(e, &e->h_cls, (size_t)d.max_images * d.dim, true));
-  TRYA(dalloc(e, &e->act_cls, (size_t)d.max_images * e->ld_int_max, true));
-  TRYA(dalloc(e, &e->logits, (size_t)d.max_images * d.classes, true));
+  const size_t pre_rows = (size_t)e->prefix * d.max_images;          // the tail's and the head's rows: prefix_tokens per image at most
+  TRYA(dalloc(e, &e->cls_h, pre_rows * d.dim, true));
+  TRYA(dalloc(e, &e->x_cls, pre_rows * d.dim, true));
+  TRYA(dalloc(e, &e->q_cls, pre_rows * d.dim, true));
+  TRYA(dalloc(e, &e->o_cls, pre_rows * d.dim, true));
+  TRYA(dalloc(e, &e->h_cls, pre_rows * d.dim, true));
+  TRYA(dalloc(e, &e->act_cls, pre_rows * e->ld_int_max, true));
+  // logits scratch: [n, classes]; with the distillation head the two heads' outputs and their mean
+  TRYA(dalloc(e, &e->logits, (size_t)(e->dist_head ? 3 : 1) * d.max_images * d.classes, true));
   TRYA(dalloc(e, &e->ln_sync, (size_t)16 + (M + 255) / 256 + 1, true));
 #ifdef SSP2_LAB
   TRYA(dalloc(e, &e->dg_scratch, (size_t)std::max(e->n_cu, 1) * 32768, true));      // 128 KiB per workgroup of the persistent GEMM (deferred residual, lab build)
@@ -903,6 +922,13 @@ static int resolve_tensor(ssp2_engine* e, int kind, int layer, IngestTarget* t) 
     case SSP2_T_LNF_B: return vec(e->lnf_b, D, &e->misc_set[3]);
     case SSP2_T_HEAD_W: return mat(e->head);
     case SSP2_T_HEAD_B: return bias(e->head);
+    case SSP2_T_DIST:
+      if (!e->dist) return fail(SSP2_EINVAL, "tensor kind %d (distillation token): this engine has one prefix token (ssp2_create_ext prefix_tokens = 2)", kind);
+      return vec(e->dist, D, &e->dist_set);
+    case SSP2_T_HEAD_DIST_W:
+    case SSP2_T_HEAD_DIST_B:
+      if (!e->dist_head) return fail(SSP2_EINVAL, "tensor kind %d (distillation head): this engine has no distillation head (ssp2_create_ext dist_head = 1)", kind);
+      return kind == SSP2_T_HEAD_DIST_W ? mat(e->head_dist) : bias(e->head_dist);
     default: return fail(SSP2_EINVAL, "unknown tensor kind %d", kind);
   }
 }
@@ -1010,6 +1036,7 @@ int ssp2_embed(ssp2_handle e, const float* pixels_dev, int n, float* x_dev, int 
   const RowMap rm = make_rowmap(e->tokens, n, group);
   if (!pixels_dev || !x_dev) return fail(SSP2_EINVAL, "null device pointer");
   if (!(e->patch.w_set && e->patch.b_set && e->misc_set[0] && e->misc_set[1])) return fail(SSP2_ESTATE, "patch/cls/pos weights not loaded");
+  if (e->prefix == 2 && !e->dist_set) return fail(SSP2_ESTATE, "distillation token not loaded (SSP2_T_DIST)");
   const int D = e->d.dim;
   if (rm.group > 0) {   // pad rows between slabs must hold finite values: they flow through LN / GEMMs (never scored).  Only THEY are
     // zeroed (one strided fill: 4.7 MB for eight 64-image ViT-B/16 slabs; round 2 cleared all 310 MB of x per stage-1 launch)
@@ -1019,7 +1046,8 @@ int ssp2_embed(ssp2_handle e, const float* pixels_dev, int n, float* x_dev, int 
   }
   {
     ProfScope ps(e, SSP2_K_OTHER);
-    hipLaunchKernelGGL(cls_row_kernel, dim3((n * D + 255) / 256), dim3(256), 0, e->stream, x_dev, e->cls, e->pos, n, rm, D);
+    hipLaunchKernelGGL(cls_row_kernel, dim3((unsigned)(((long)n * e->prefix * D + 255) / 256)), dim3(256), 0, e->stream, x_dev, e->cls, e->pos, n, rm, D,
+                       e->dist, e->prefix);
     HIPCHK(hipGetLastError());
   }
   if (e->opt[SSP2_OPT_PATCH_LDS]) {
@@ -1028,7 +1056,7 @@ int ssp2_embed(ssp2_handle e, const float* pixels_dev, int n, float* x_dev, int 
     PatchArgs a{};
     a.px = pixels_dev; a.W = e->patch.w; a.ldw = e->patch.ld; a.bias = e->patch.b; a.pos = e->pos; a.x = x_dev; a.ldx = D;
     a.n = n; a.img = e->d.img; a.p = e->d.patch; a.side = e->side; a.K = e->kpe; a.Kpad = e->kpe_pad; a.N = D;
-    a.tiles_n = e->patch.rows_pad / GEMM_BN; a.rm = rm;
+    a.tiles_n = e->patch.rows_pad / GEMM_BN; a.rm = rm; a.prefix = e->prefix;
     const int tiles_m = (n * e->patches + GEMM_BM - 1) / GEMM_BM;
     static bool attr_done[kMaxDevices] = {};
     if (!attr_done[e->dev]) {
@@ -1057,7 +1085,7 @@ int ssp2_embed(ssp2_handle e, const float* pixels_dev, int n, float* x_dev, int 
   GemmArgs g{};
   g.A = e->a_pe; g.lda = e->kpe_pad; g.W = e->patch.w; g.ldw = e->patch.ld; g.bias = e->patch.b;
   g.M = n * e->patches; g.N = D; g.K = e->kpe_pad; g.tiles_n = e->patch.rows_pad / GEMM_BN;
-  g.x = x_dev; g.ldx = D; g.pos = e->pos; g.patches = e->patches; g.group = rm.group; g.mpad = rm.mpad; g.n_img = n;
+  g.x = x_dev; g.ldx = D; g.pos = e->pos; g.patches = e->patches; g.prefix = e->prefix; g.group = rm.group; g.mpad = rm.mpad; g.n_img = n;
   return launch_gemm<EPI_PATCH>(e, g, SSP2_K_GEMM_PATCH);
 }
 
@@ -1256,20 +1284,42 @@ int ssp2_layers_prefix(ssp2_handle e, const float* x_in, float* x, int n, int l_
   return 0;
 }
 
+// The head on the rows it reads: row 0 of every image (CLS), and row 1 (DIST) too with the distillation head.  x holds them either
+// where ssp2_embed put them (prefix_major = false: image r's prefix row t at x + t * D + r * in_stride, or through the row map `gather`),
+// or already compacted prefix-major [tail_rows][n][D] at a row stride of in_stride (prefix_major = true: the tail's x_cls).
 static int head_impl(ssp2_engine* e, const float* x, size_t in_stride, int n, float* logits_dev, int32_t* pred, const int64_t* labels,
-                     int64_t* correct, RowMap gather = RowMap{0, 0, 0}, int period = 0) {
+                     int64_t* correct, RowMap gather = RowMap{0, 0, 0}, int period = 0, bool prefix_major = false) {
   int rc;
   if (!(e->misc_set[2] && e->misc_set[3] && e->head.w_set && e->head.b_set)) return fail(SSP2_ESTATE, "final norm / head weights not loaded");
-  const int D = e->d.dim;
-  if ((rc = launch_ln(e, x, in_stride, e->lnf_g, e->lnf_b, e->cls_h, D, n, D, gather))) return rc;
-  float* lg = logits_dev ? logits_dev : e->logits;
+  if (e->dist_head && !(e->head_dist.w_set && e->head_dist.b_set)) return fail(SSP2_ESTATE, "distillation head weights not loaded");
+  const int D = e->d.dim, C = e->d.classes, hr = e->tail_rows;
+  if (prefix_major) {
+    if ((rc = launch_ln(e, x, in_stride, e->lnf_g, e->lnf_b, e->cls_h, D, hr * n, D, gather))) return rc;
+  } else {
+    for (int t = 0; t < hr; ++t)
+      if ((rc = launch_ln(e, x + (size_t)t * D, in_stride, e->lnf_g, e->lnf_b, e->cls_h + (size_t)t * n * D, D, n, D, gather))) return rc;
+  }
+  float* lg = e->dist_head ? e->logits : (logits_dev ? logits_dev : e->logits);
   GemmArgs g{};
   g.A = e->cls_h; g.lda = D; g.W = e->head.w; g.ldw = e->head.ld; g.bias = e->head.b;
-  g.M = n; g.N = e->d.classes; g.K = D; g.tiles_n = e->head.rows_pad / GEMM_BN; g.x = lg; g.ldx = e->d.classes;
+  g.M = n; g.N = C; g.K = D; g.tiles_n = e->head.rows_pad / GEMM_BN; g.x = lg; g.ldx = C;
   if ((rc = launch_gemm<EPI_F32>(e, g, SSP2_K_GEMM_HEAD))) return rc;
+  if (e->dist_head) {   // head_dist on the DIST rows, then logits = 0.5f * bf16(a + b) (autocast's rounding points) and the top-1 of the mean in one kernel
+    float* lb = e->logits + (size_t)n * C;
+    float* out = logits_dev ? logits_dev : e->logits + (size_t)2 * n * C;
+    GemmArgs h{};
+    h.A = e->cls_h + (size_t)n * D; h.lda = D; h.W = e->head_dist.w; h.ldw = e->head_dist.ld; h.bias = e->head_dist.b;
+    h.M = n; h.N = C; h.K = D; h.tiles_n = e->head_dist.rows_pad / GEMM_BN; h.x = lb; h.ldx = C;
+    if ((rc = launch_gemm<EPI_F32>(e, h, SSP2_K_GEMM_HEAD))) return rc;
+    ProfScope ps(e, SSP2_K_OTHER);
+    hipLaunchKernelGGL(dist_head_top1_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, lg, lb, out, n, C, pred, labels,
+                       (unsigned long long*)correct, period);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   if (pred || (labels && correct)) {
     ProfScope ps(e, SSP2_K_OTHER);
-    hipLaunchKernelGGL(argmax_top1_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, lg, n, e->d.classes, pred, labels,
+    hipLaunchKernelGGL(argmax_top1_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, lg, n, C, pred, labels,
                        (unsigned long long*)correct, period);
     HIPCHK(hipGetLastError());
   }
@@ -1313,45 +1363,48 @@ int ssp2_tail_group(ssp2_handle e, const float* x, int n_slot, int slots, int gr
   const RowMap rm = make_rowmap(e->tokens, n, group);
   if (rm.group > 0 && slots > 1 && n_slot % rm.group != 0) return fail(SSP2_EINVAL, "tail: slots of %d images are not whole slabs of %d", n_slot, group);
   const int D = e->d.dim, M = (int)total_rows(rm, n), l = e->d.depth - 1;
+  const int P = e->tail_rows, PN = P * n;              // rows the tail carries: CLS, and DIST with the distillation head
   Layer& L = e->layers[l];
   if (!(L.ln_set[2] && L.ln_set[3] && L.fc1.w_set && L.fc1.b_set && L.fc2.w_set && L.fc2.b_set)) return fail(SSP2_ESTATE, "last layer MLP weights not loaded");
-  // x_cls <- CLS rows of x (x itself is left untouched)
+  // x_cls <- prefix rows 0..P-1 of x, prefix-major [P][n][D] (x itself is left untouched)
   if (rm.group > 0) {
     ProfScope ps(e, SSP2_K_OTHER);
-    hipLaunchKernelGGL(gather_cls_rows_kernel, dim3((unsigned)(((long)n * (D / 4) + 255) / 256)), dim3(256), 0, e->stream, x, e->x_cls, n, rm, D);
+    hipLaunchKernelGGL(gather_cls_rows_kernel, dim3((unsigned)(((long)PN * (D / 4) + 255) / 256)), dim3(256), 0, e->stream, x, e->x_cls, n, rm, D, P);
     HIPCHK(hipGetLastError());
   } else {
-    HIPCHK(hipMemcpy2DAsync(e->x_cls, (size_t)D * 4, x, (size_t)e->tokens * D * 4, (size_t)D * 4, n, hipMemcpyDeviceToDevice, e->stream));
+    for (int t = 0; t < P; ++t)
+      HIPCHK(hipMemcpy2DAsync(e->x_cls + (size_t)t * n * D, (size_t)D * 4, x + (size_t)t * D, (size_t)e->tokens * D * 4, (size_t)D * 4, n,
+                              hipMemcpyDeviceToDevice, e->stream));
   }
   if (!attn_skip_last && !L.attn_dropped) {
     if (!(L.ln_set[0] && L.ln_set[1] && L.qkv.w_set && L.qkv.b_set && L.proj.w_set && L.proj.b_set)) return fail(SSP2_ESTATE, "last layer attention weights not loaded");
-    // keys / values need every token; the query, the out-projection and the MLP only the CLS row
+    // keys / values need every token; the query, the out-projection and the MLP only the P prefix rows
     if ((rc = launch_ln(e, x, D, L.ln1_g, L.ln1_b, e->hbuf, D, M, D))) return rc;
     GemmArgs kv{};
     kv.A = e->hbuf; kv.lda = D; kv.W = L.qkv.w + (size_t)D * L.qkv.ld; kv.ldw = L.qkv.ld; kv.bias = L.qkv.b + D;
     kv.M = M; kv.N = 2 * D; kv.K = D; kv.tiles_n = (2 * D + GEMM_BN - 1) / GEMM_BN; kv.out = e->qkvbuf + D; kv.ldo = 3 * D;
     if ((rc = launch_gemm<EPI_BF16>(e, kv, SSP2_K_GEMM_QKV))) return rc;
-    if ((rc = launch_ln(e, x, (size_t)e->tokens * D, L.ln1_g, L.ln1_b, e->h_cls, D, n, D, rm.group > 0 ? rm : RowMap{0, 0, 0}))) return rc;
+    if ((rc = launch_ln(e, e->x_cls, D, L.ln1_g, L.ln1_b, e->h_cls, D, PN, D))) return rc;     // the same rows' bits as the full LN1
     GemmArgs q{};
     q.A = e->h_cls; q.lda = D; q.W = L.qkv.w; q.ldw = L.qkv.ld; q.bias = L.qkv.b;
-    q.M = n; q.N = D; q.K = D; q.tiles_n = (D + GEMM_BN - 1) / GEMM_BN; q.out = e->q_cls; q.ldo = D;
+    q.M = PN; q.N = D; q.K = D; q.tiles_n = (D + GEMM_BN - 1) / GEMM_BN; q.out = e->q_cls; q.ldo = D;
     if ((rc = launch_gemm<EPI_BF16>(e, q, SSP2_K_GEMM_QKV))) return rc;
     if ((rc = launch_attn(e, n, rm, true))) return rc;
     GemmArgs p{};
     p.A = e->o_cls; p.lda = D; p.W = L.proj.w; p.ldw = L.proj.ld; p.bias = L.proj.b;
-    p.M = n; p.N = D; p.K = D; p.tiles_n = L.proj.rows_pad / GEMM_BN; p.x = e->x_cls; p.ldx = D;
+    p.M = PN; p.N = D; p.K = D; p.tiles_n = L.proj.rows_pad / GEMM_BN; p.x = e->x_cls; p.ldx = D;
     if ((rc = launch_gemm<EPI_RESID>(e, p, SSP2_K_GEMM_PROJ))) return rc;
   }
-  if ((rc = launch_ln(e, e->x_cls, D, L.ln2_g, L.ln2_b, e->h_cls, D, n, D))) return rc;
+  if ((rc = launch_ln(e, e->x_cls, D, L.ln2_g, L.ln2_b, e->h_cls, D, PN, D))) return rc;
   GemmArgs f{};
   f.A = e->h_cls; f.lda = D; f.W = L.fc1.w; f.ldw = L.fc1.ld; f.bias = L.fc1.b;
-  f.M = n; f.N = L.ld_int; f.K = D; f.tiles_n = L.fc1.rows_pad / GEMM_BN; f.out = e->act_cls; f.ldo = L.ld_int;
+  f.M = PN; f.N = L.ld_int; f.K = D; f.tiles_n = L.fc1.rows_pad / GEMM_BN; f.out = e->act_cls; f.ldo = L.ld_int;
   if ((rc = launch_gemm<EPI_FC1, 0>(e, f, SSP2_K_GEMM_FC1))) return rc;
   GemmArgs o{};
   o.A = e->act_cls; o.lda = L.ld_int; o.W = L.fc2.w; o.ldw = L.fc2.ld; o.bias = L.fc2.b;
-  o.M = n; o.N = D; o.K = L.ld_int; o.tiles_n = L.fc2.rows_pad / GEMM_BN; o.x = e->x_cls; o.ldx = D;
+  o.M = PN; o.N = D; o.K = L.ld_int; o.tiles_n = L.fc2.rows_pad / GEMM_BN; o.x = e->x_cls; o.ldx = D;
   if ((rc = launch_gemm<EPI_RESID>(e, o, SSP2_K_GEMM_FC2))) return rc;
-  return head_impl(e, e->x_cls, (size_t)D, n, logits_dev, pred, labels, correct, RowMap{0, 0, 0}, period);
+  return head_impl(e, e->x_cls, (size_t)D, n, logits_dev, pred, labels, correct, RowMap{0, 0, 0}, period, true);
 }
 
 int ssp2_d_int(ssp2_handle e, int layer) {
@@ -1463,12 +1516,16 @@ int ssp2_clone_weights(ssp2_handle dst, ssp2_handle src) {
   const ssp2_vit_desc &a = dst->d, &b = src->d;
   if (a.img != b.img || a.patch != b.patch || a.dim != b.dim || a.heads != b.heads || a.depth != b.depth || a.classes != b.classes)
     return fail(SSP2_EINVAL, "clone: the two engines describe different architectures");
+  if (dst->prefix != src->prefix || dst->dist_head != src->dist_head)
+    return fail(SSP2_EINVAL, "clone: token layouts differ (prefix_tokens %d / %d, dist_head %d / %d)", dst->prefix, src->prefix, dst->dist_head, src->dist_head);
   const int D = a.dim;
   int rc;
   auto cp = [&](float* d, const float* s, size_t n) -> int { HIPCHK(hipMemcpyAsync(d, s, n * 4, hipMemcpyDeviceToDevice, dst->stream)); return 0; };
   if ((rc = copy_mat(dst, dst->patch, src->patch)) || (rc = copy_mat(dst, dst->head, src->head))) return rc;
   if ((rc = cp(dst->cls, src->cls, D)) || (rc = cp(dst->pos, src->pos, (size_t)dst->tokens * D)) || (rc = cp(dst->lnf_g, src->lnf_g, D)) || (rc = cp(dst->lnf_b, src->lnf_b, D))) return rc;
   for (int i = 0; i < 4; ++i) dst->misc_set[i] = src->misc_set[i];
+  if (src->dist) { if ((rc = cp(dst->dist, src->dist, D))) return rc; dst->dist_set = src->dist_set; }
+  if (src->dist_head && (rc = copy_mat(dst, dst->head_dist, src->head_dist))) return rc;
   for (int l = 0; l < a.depth; ++l) {
     Layer &d = dst->layers[l]; const Layer& s = src->layers[l];
     if ((rc = cp(d.ln1_g, s.ln1_g, D)) || (rc = cp(d.ln1_b, s.ln1_b, D)) || (rc = cp(d.ln2_g, s.ln2_g, D)) || (rc = cp(d.ln2_b, s.ln2_b, D))) return rc;
@@ -1612,6 +1669,31 @@ int ssp2_attention_stream_bf16(void* hip_stream, const uint16_t* qkv_dev, int n,
   e.qkvbuf = (bf16*)qkv_dev; e.q_cls = (bf16*)q_cls_dev;
   e.obuf = e.o_cls = (bf16*)out_dev; e.o_ld = ldo;
   return launch_attn_stream(&e, n, make_rowmap(tokens, n, group), q_cls_dev != nullptr);
+}
+
+// The tail's prefix-query attention on its own (n_prefix queries per image, prefix-major q and out), on the resident CLS-only kernels or,
+// stream != 0, the key-streaming one: a temporary engine whose tail carries n_prefix rows, then the forward's launch.
+int ssp2_attention_prefix_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
+                               const uint16_t* q_dev, uint16_t* out_dev, int ldo, int n_prefix, int stream) {
+  if (!qkv_dev || !q_dev || !out_dev) return fail(SSP2_EINVAL, "attention_prefix: null qkv / q / out");
+  if (n <= 0 || heads <= 0 || tokens <= 0 || group < 0) return fail(SSP2_EINVAL, "attention_prefix: n=%d heads=%d tokens=%d group=%d", n, heads, tokens, group);
+  if (n_prefix < 1 || n_prefix > 2) return fail(SSP2_EINVAL, "attention_prefix: n_prefix=%d (1 or 2)", n_prefix);
+  if (n_prefix > tokens) return fail(SSP2_EINVAL, "attention_prefix: n_prefix=%d > tokens=%d", n_prefix, tokens);
+  if (stream < 0 || stream > 1) return fail(SSP2_EINVAL, "attention_prefix: stream=%d (0 resident, 1 key-streaming)", stream);
+  if (stream ? !attn_stream_ok(d_h, tokens) : !attn_resident(d_h, tokens))
+    return fail(SSP2_EINVAL, "attention_prefix: no %s kernel for d_h=%d, tokens=%d", stream ? "key-streaming" : "resident", d_h, tokens);
+  if ((long)heads * d_h > (1 << 20) || (heads * d_h) % 8) return fail(SSP2_EINVAL, "attention_prefix: dim = heads * d_h = %ld (a multiple of 8)", (long)heads * d_h);
+  const int dim = heads * d_h;
+  if (ldo < dim || ldo % 8) return fail(SSP2_EINVAL, "attention_prefix: ldo=%d (>= dim %d, a multiple of 8)", ldo, dim);
+  if ((long)n * heads > 0x7fffffffL || (long)n_prefix * n * ldo > 0x7fffffffL || (long)n * dim > 0x7fffffffL)
+    return fail(SSP2_EINVAL, "attention_prefix: n=%d too large", n);
+  ssp2_engine e;
+  e.d.dim = dim; e.d.heads = heads; e.tokens = tokens; e.dh = d_h; e.tail_rows = n_prefix;
+  e.opt[SSP2_OPT_ATTN_STREAM] = stream ? 2 : 0;
+  e.stream = (hipStream_t)hip_stream; e.n_cu = op_cu_count(); e.dev = cur_device();
+  e.qkvbuf = (bf16*)qkv_dev; e.q_cls = (bf16*)q_dev;
+  e.obuf = e.o_cls = (bf16*)out_dev; e.o_ld = ldo;
+  return launch_attn(&e, n, make_rowmap(tokens, n, group), true);
 }
 
 // LayerNorm on its own, on caller-owned buffers: launch_ln of a temporary engine (the forward's MAXV / FULL dispatch and its

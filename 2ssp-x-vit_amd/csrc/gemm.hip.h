@@ -20,7 +20,7 @@
 //   EPI_RESID  x  += float(bf16(acc + bias))                            attention out-proj, fc2 (+residual)
 //   EPI_FC1    pre = bf16(acc + bias); out = bf16(gelu(pre));           fc1 + GELU + fused stage-1 score:
 //              per-(sample, neuron) partial sum of squares over this tile's tokens -> slab (2 segments/tile)
-//   EPI_PATCH  x[img*N + 1 + p] = float(bf16(acc + bias)) + pos[1 + p]  patch-embed conv as GEMM
+//   EPI_PATCH  x[img*N + P + p] = float(bf16(acc + bias)) + pos[P + p]  patch-embed conv as GEMM (P = prefix tokens: CLS [+ DIST])
 //   EPI_F32    out_f32 = float(bf16(acc + bias))                        classifier head (tiny, scalar stores)
 #pragma once
 #include "common.hip.h"
@@ -51,7 +51,7 @@ struct GemmArgs {
   int group, mpad, n_img;     // slab layout of the rows (RowMap); group == 0: contiguous
   float* slab; int slab_ld;   // [tiles_m][2][slab_ld]
   // EPI_PATCH
-  const float* pos; int patches;
+  const float* pos; int patches; int prefix;   // prefix: tokens in front of the patches (1: CLS; 2: CLS + DIST)
   int group_m;                // row tiles per L2 super-tile (0 = plain N-fastest order)
   int nt_out;                 // gemm256 kernel: bf16 / e4m3 activation outputs leave as NON-TEMPORAL stores (SSP2_OPT_NT_STORES)
   int reverse;                // gemm256: walk the tiles from the last to the first (see engine.hip, zigzag)
@@ -433,9 +433,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs g) {
         xin[it] = *(const f32x4*)((g.xin ? g.xin : g.x) + (size_t)mc * g.ldx + col0 + c);
       } else {
         const int img = mc / g.patches, p = mc - img * g.patches;
-        const RowMap rm{g.patches + 1, g.group, g.mpad};
-        dst[it] = g.x + (size_t)(row_of(rm, img) + 1 + p) * g.ldx + col0 + c;
-        xin[it] = *(const f32x4*)(g.pos + (size_t)(1 + p) * g.ldx + col0 + c);
+        const RowMap rm{g.patches + g.prefix, g.group, g.mpad};
+        dst[it] = g.x + (size_t)(row_of(rm, img) + g.prefix + p) * g.ldx + col0 + c;
+        xin[it] = *(const f32x4*)(g.pos + (size_t)(g.prefix + p) * g.ldx + col0 + c);
       }
     }
 #pragma unroll

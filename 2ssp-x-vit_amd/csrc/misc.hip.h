@@ -43,21 +43,25 @@ __global__ void xcc_probe_kernel(unsigned int* __restrict__ ids) {
 }
 
 __global__ void cls_row_kernel(float* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos,
-                               int n, RowMap rm, int dim) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n * dim) {
-    const int im = i / dim, d = i - im * dim;
-    x[(size_t)row_of(rm, im) * dim + d] = cls[d] + pos[d];
+                               int n, RowMap rm, int dim, const float* __restrict__ dist = nullptr, int prefix = 1) {
+  // prefix rows of every image: row 0 = cls + pos[0], row 1 (distilled models) = dist + pos[1]
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (long)n * prefix * dim) {
+    const int r = (int)(i / dim), d = (int)(i - (long)r * dim);
+    const int im = r / prefix, t = r - im * prefix;
+    x[(size_t)(row_of(rm, im) + t) * dim + d] = (t ? dist : cls)[d] + pos[(size_t)t * dim + d];
   }
 }
 
-// CLS rows of a residual stream in the slab layout -> compact [n, dim] fp32 (the tail of the search; the contiguous layout uses a 2-D copy)
-__global__ void gather_cls_rows_kernel(const float* __restrict__ x, float* __restrict__ out, int n, RowMap rm, int dim) {
+// prefix rows of a residual stream in the slab layout -> compact fp32, prefix-major: out[t][im] = row t of image im, t < prefix
+// (the tail of the search; the contiguous layout uses a 2-D copy per prefix row)
+__global__ void gather_cls_rows_kernel(const float* __restrict__ x, float* __restrict__ out, int n, RowMap rm, int dim, int prefix = 1) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int q = dim / 4;
-  if (i < (long)n * q) {
-    const int im = (int)(i / q), c = (int)(i - (long)im * q);
-    ((f32x4*)out)[i] = ((const f32x4*)(x + (size_t)row_of(rm, im) * dim))[c];
+  if (i < (long)prefix * n * q) {
+    const int r = (int)(i / q), c = (int)(i - (long)r * q);
+    const int t = r / n, im = r - t * n;
+    ((f32x4*)out)[i] = ((const f32x4*)(x + (size_t)(row_of(rm, im) + t) * dim))[c];
   }
 }
 
@@ -328,6 +332,42 @@ __global__ __launch_bounds__(256) void argmax_top1_kernel(const float* __restric
     if (take) { best = ob; bi = oi; bnan = (bool)on; }
   }
   if (lane == 0) {
+    if (pred) pred[row] = bi;
+    if (labels && correct) {
+      const int li = period > 0 ? row % period : row, ci = period > 0 ? row / period : 0;
+      if (labels[li] == (int64_t)bi) atomicAdd(correct + ci, 1ULL);
+    }
+  }
+}
+
+// Distilled head (DeiT, eval mode): logits = (head(CLS) + head_dist(DIST)) / 2 of the two EPI_F32 head GEMMs a and b (bf16-representable
+// values), with the rounding points of the reference's autocast arithmetic: the bf16 sum, then the halving (exact in bf16) — written as
+// 0.5f * bf16(a + b) to `logits` — then pred / correct by exactly the rule of argmax_top1_kernel (first maximum, NaN first, `period`).
+__global__ __launch_bounds__(256) void dist_head_top1_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ logits,
+                                                            int n, int classes, int32_t* __restrict__ pred, const int64_t* __restrict__ labels,
+                                                            unsigned long long* __restrict__ correct, int period = 0) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  const size_t off = (size_t)row * classes;
+  float best = -INFINITY; int bi = 0x7fffffff; bool bnan = false;
+  for (int c = lane; c < classes; c += 64) {
+    const float v = 0.5f * bf16_round(a[off + c] + b[off + c]);
+    logits[off + c] = v;
+    const bool vnan = v != v;
+    if (vnan && !bnan) { bnan = true; bi = c; }          // first NaN wins for this lane (the loop goes on: every logit is written)
+    if (!bnan && (v > best || bi == 0x7fffffff)) { best = v; bi = c; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o); const int on = __shfl_xor((int)bnan, o);
+    bool take;
+    if (bnan != (bool)on) take = (bool)on;
+    else if (bnan) take = oi < bi;
+    else take = (ob > best) || (ob == best && oi < bi);
+    if (take) { best = ob; bi = oi; bnan = (bool)on; }
+  }
+  if (lane == 0 && (pred || (labels && correct))) {
     if (pred) pred[row] = bi;
     if (labels && correct) {
       const int li = period > 0 ? row % period : row, ci = period > 0 ? row / period : 0;

@@ -1,6 +1,6 @@
 // Patch embedding (conv k = s = p as a GEMM) with the patch tiles staged through LDS straight from the fp32 pixels:
 //
-//   x[row(img) + 1 + q, :] = float(bf16(sum_k bf16(pixel[img, q, k]) * W[:, k] + bias)) + pos[1 + q, :]
+//   x[row(img) + P + q, :] = float(bf16(sum_k bf16(pixel[img, q, k]) * W[:, k] + bias)) + pos[P + q, :]   (P = prefix tokens: 1, or 2 with a distillation token)
 //
 // Round 1-2 went pixels -> im2col_patch_kernel -> bf16 matrix in HBM (154 MB per 512 images, written and read back) ->
 // gemm_bf16_kernel<EPI_PATCH>.  Here the A operand never exists in HBM: a workgroup gathers its 128 patches x 64 k-elements
@@ -21,7 +21,8 @@ struct PatchArgs {
   float* x; int ldx;          // residual stream, row layout rm
   int n, img, p, side, K, Kpad, N;
   int tiles_n;
-  RowMap rm;                  // tokens = patches + 1
+  RowMap rm;                  // tokens = patches + prefix
+  int prefix;                 // tokens in front of the patches (1: CLS; 2: CLS + distillation token)
 };
 
 #define PATCH_LDS_BYTES (4 * GEMM_STAGE_BYTES)     // A0 A1 B0 B1; the fp32 epilogue staging (4 x 16 KiB) reuses all of it
@@ -199,8 +200,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (m < M) {
       const int im = m / patches, q = m - im * patches;
       const f32x4 v = *(const f32x4*)(stg + r * 256 + c * 4);
-      const f32x4 ps = *(const f32x4*)(g.pos + (size_t)(1 + q) * g.ldx + col0 + c);
-      *(f32x4*)(g.x + (size_t)(row_of(g.rm, im) + 1 + q) * g.ldx + col0 + c) = ps + v;
+      const f32x4 ps = *(const f32x4*)(g.pos + (size_t)(g.prefix + q) * g.ldx + col0 + c);
+      *(f32x4*)(g.x + (size_t)(row_of(g.rm, im) + g.prefix + q) * g.ldx + col0 + c) = ps + v;
     }
   }
 }

@@ -24,11 +24,12 @@ SYMBOLS = [
     "ssp2_embed", "ssp2_layers", "ssp2_layers_from", "ssp2_layers_prefix", "ssp2_head", "ssp2_tail", "ssp2_tail_slots", "ssp2_tail_group", "ssp2_prune_ffn", "ssp2_drop_attention", "ssp2_d_int", "ssp2_act_l2_accum", "ssp2_profile_begin", "ssp2_profile_end",
     "ssp2_tokens", "ssp2_rows", "ssp2_workspace_bytes", "ssp2_preproc_create", "ssp2_preproc_run", "ssp2_preproc_destroy",
     "ssp2_fp8_calibrate_begin", "ssp2_fp8_calibrate_end", "ssp2_fp8_attn_scale", "ssp2_fp8_set_attn_scale",
-    "ssp2_create_opts", "ssp2_attention_stream_bf16",
+    "ssp2_create_opts", "ssp2_attention_stream_bf16", "ssp2_create_ext", "ssp2_attention_prefix_bf16",
 ]
 
 T_KINDS = ["patch_w", "patch_b", "cls", "pos", "ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b",
-           "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "lnf_g", "lnf_b", "head_w", "head_b"]
+           "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "lnf_g", "lnf_b", "head_w", "head_b",
+           "dist", "head_dist_w", "head_dist_b"]                # (the last three: distilled models, ssp2_create_ext)
 SCORE_SITE = {"none": 0, "pre_gelu": 1, "post_gelu": 2}
 SCORE_CHAIN = {"fp32": 0, "bf16_ref": 1}
 OPTIONS = {"zigzag": 0, "attn_persist": 1, "ln_fusion": 2, "big_tiles": 3, "fc1_big_tiles": 4, "group256": 5, "patch_lds": 6, "attn_stagger": 7, "fp8_proj": 8, "big_tile_min_rows": 9, "nt_stores": 10, "defer_resid": 11, "attn_live": 12, "attn_stream": 13}   # SSP2_OPT_*
@@ -42,6 +43,11 @@ class VitDesc(C.Structure):
     _fields_ = [("img", C.c_int32), ("patch", C.c_int32), ("dim", C.c_int32), ("heads", C.c_int32),
                 ("depth", C.c_int32), ("classes", C.c_int32), ("ln_eps", C.c_float), ("max_images", C.c_int32),
                 ("d_int", C.POINTER(C.c_int32))]
+
+
+class VitExt(C.Structure):
+    """ssp2_vit_ext: the token layout of ssp2_create_ext (prefix tokens 1 / 2, distillation head 0 / 1)."""
+    _fields_ = [("prefix_tokens", C.c_int32), ("dist_head", C.c_int32)]
 
 
 class Ssp2Error(RuntimeError):
@@ -216,6 +222,7 @@ def load(build_if_missing: bool = True, variant: Optional[str] = None) -> C.CDLL
     lib.ssp2_last_error.restype = C.c_char_p
     lib.ssp2_create.argtypes = [C.POINTER(VitDesc), C.POINTER(vp)]
     lib.ssp2_create_opts.argtypes = [C.POINTER(VitDesc), C.POINTER(i32), C.POINTER(vp)]
+    lib.ssp2_create_ext.argtypes = [C.POINTER(VitDesc), C.POINTER(i32), C.POINTER(VitExt), C.POINTER(vp)]
     lib.ssp2_destroy.argtypes = [vp]
     lib.ssp2_set_stream.argtypes = [vp, vp]
     lib.ssp2_load_tensor.argtypes = [vp, i32, i32, C.POINTER(C.c_float), C.c_size_t]
@@ -224,6 +231,7 @@ def load(build_if_missing: bool = True, variant: Optional[str] = None) -> C.CDLL
     lib.ssp2_linear_bf16.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, vp, i32, i32]
     lib.ssp2_attention_bf16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, C.c_float, vp, i32, i32, i32]
     lib.ssp2_attention_stream_bf16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32]
+    lib.ssp2_attention_prefix_bf16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32]
     lib.ssp2_layernorm.argtypes = [vp, vp, C.c_size_t, i32, i32, vp, vp, C.c_float, i32, i32, vp, i32, vp, vp, i32]
     lib.ssp2_embed.argtypes = [vp, vp, i32, vp, i32]
     lib.ssp2_rows.argtypes = [vp, i32, i32]

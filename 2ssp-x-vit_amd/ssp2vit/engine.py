@@ -9,7 +9,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import K_CLASS, OPTIONS, SCORE_CHAIN, SCORE_SITE, T_KINDS, Ssp2Error, VitDesc, check
+from ._lib import K_CLASS, OPTIONS, SCORE_CHAIN, SCORE_SITE, T_KINDS, Ssp2Error, VitDesc, VitExt, check
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -36,7 +36,9 @@ class VitEngine:
         does not instantiate (options ln_fusion / defer_resid / group256; ssp2vit/_lib.py VARIANT_FLAGS).
         `attn_stream`: SSP2_OPT_ATTN_STREAM in force when the engine is created (None: the environment's SSP2_ATTN_STREAM, default 0).
         0 = resident attention kernels only (d_h = 64 up to 288 tokens); 1 = longer d_h = 64 sequences (384-pixel /16: 577 tokens,
-        224-pixel /8: 785) on the key-streaming kernel; 2 = every d_h = 64 attention streams (cross-checks).  A twin inherits it."""
+        224-pixel /8: 785) on the key-streaming kernel; 2 = every d_h = 64 attention streams (cross-checks).  A twin inherits it.
+        Token layout: `weights["prefix_tokens"]` (default 1; 2 = CLS + distillation token, DeiT) and a distillation head when the
+        dictionary has `head_dist_w` (logits = mean of the CLS and DIST heads) go to ssp2_create_ext; a twin inherits them too."""
         if precision not in ("bf16", "fp8"):
             raise ValueError(f"precision must be 'bf16' or 'fp8', got {precision!r}")
         if attn_stream is not None and (isinstance(attn_stream, bool) or attn_stream not in (0, 1, 2)):
@@ -46,7 +48,8 @@ class VitEngine:
             src = _twin_of
             attn_stream = src.attn_stream
             weights = dict(depth=src.depth, dim=src.dim, classes=src.classes, img=src.img, patch=src.patch, heads=src.heads,
-                           eps=src.eps, **{f"fc1_w.{i}": torch.empty(int(d), 0) for i, d in enumerate(_d_int)})
+                           eps=src.eps, prefix_tokens=src.prefix_tokens, dist_head=src.dist_head,
+                           **{f"fc1_w.{i}": torch.empty(int(d), 0) for i, d in enumerate(_d_int)})
             device = src.device
         if not torch.cuda.is_available():
             raise Ssp2Error("ssp2vit needs an MI355X (HIP device): there is no CPU fallback in the product path")
@@ -62,6 +65,8 @@ class VitEngine:
         self.classes = int(weights["classes"])
         self.img = int(weights["img"])
         self.patch, self.heads, self.eps = int(weights["patch"]), int(weights["heads"]), float(weights.get("eps", 1e-6))
+        self.prefix_tokens = int(weights.get("prefix_tokens", 1))
+        self.dist_head = int(weights.get("dist_head", "head_dist_w" in weights))
         self.d_int = [int(weights[f"fc1_w.{i}"].shape[0]) for i in range(self.depth)]
         self.score_ld = max((d + 63) // 64 * 64 for d in self.d_int)
         self.max_images = int(max_images)
@@ -74,7 +79,11 @@ class VitEngine:
             opts = (C.c_int32 * _lib.OPT_COUNT)(*([-1] * _lib.OPT_COUNT))
             if attn_stream is not None:
                 opts[OPTIONS["attn_stream"]] = int(attn_stream)
-            self._check(self.lib.ssp2_create_opts(C.byref(desc), opts, C.byref(h)))
+            if self.prefix_tokens == 1 and not self.dist_head:
+                self._check(self.lib.ssp2_create_opts(C.byref(desc), opts, C.byref(h)))
+            else:
+                ext = VitExt(self.prefix_tokens, self.dist_head)
+                self._check(self.lib.ssp2_create_ext(C.byref(desc), opts, C.byref(ext), C.byref(h)))
             self.h = h
             self.tokens = self.lib.ssp2_tokens(self.h)
             self.attn_stream = self.get_option("attn_stream")
@@ -108,6 +117,10 @@ class VitEngine:
                                                 C.cast(t.data_ptr(), C.POINTER(C.c_float)), t.numel()))
         for k in ("patch_w", "patch_b", "cls", "pos", "lnf_g", "lnf_b", "head_w", "head_b"):
             put(k, 0, w[k])
+        if self.prefix_tokens == 2:
+            put("dist", 0, w["dist"])
+        if self.dist_head:
+            put("head_dist_w", 0, w["head_dist_w"]); put("head_dist_b", 0, w["head_dist_b"])
         for i in range(self.depth):
             for k in ("ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ln2_g", "ln2_b",
                       "fc1_w", "fc1_b", "fc2_w", "fc2_b"):
@@ -126,7 +139,7 @@ class VitEngine:
     def geometry_key(self):
         """What two engines must share for one to take over the other's handle (workspace, weight storage): see `reload`."""
         return (str(self.device), self.precision, self.lib_variant, self.img, self.patch, self.dim, self.heads, self.depth, self.classes,
-                float(self.eps), tuple(int(d) for d in self.d_int))
+                float(self.eps), tuple(int(d) for d in self.d_int), self.prefix_tokens, self.dist_head)
 
     def reload(self, weights: Dict) -> "VitEngine":
         """Another model of the SAME geometry into this engine: every tensor is ingested again (device-to-device rounding kernels), the
@@ -137,6 +150,8 @@ class VitEngine:
             raise Ssp2Error("reload: bf16 engines only (an fp8 engine carries quantised weight images and calibrated scales)")
         if [int(weights[f"fc1_w.{i}"].shape[0]) for i in range(self.depth)] != [int(d) for d in self.d_int]:
             raise Ssp2Error("reload: FFN widths differ")
+        if (int(weights.get("prefix_tokens", 1)), int(weights.get("dist_head", "head_dist_w" in weights))) != (self.prefix_tokens, self.dist_head):
+            raise Ssp2Error("reload: token layouts differ (prefix tokens / distillation head)")
         with torch.cuda.device(self.device):
             self._load(weights)
             for l in range(self.depth):
@@ -482,6 +497,27 @@ class VitEngine:
             raise ValueError(f"output [{tuple(out.shape)}] smaller than [{need}, {dim}]")
         self._check(self.lib.ssp2_attention_stream_bf16(C.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream), _ptr(qkv), n, tokens,
                                                         heads, d_h, group, _ptr(q_cls), _ptr(out), out.stride(0)))
+        return out
+
+    def attention_prefix(self, qkv: torch.Tensor, n: int, tokens: int, heads: int, d_h: int, q: torch.Tensor, n_prefix: int, *,
+                         group: int = 0, out: Optional[torch.Tensor] = None, stream: bool = False) -> torch.Tensor:
+        """The evaluation tail's prefix-query attention on its own (ssp2_attention_prefix_bf16): n_prefix (1 or 2) queries per image,
+        q bf16 [n_prefix * n, dim] prefix-major (row t * n + i = prefix query t of image i), densely packed; qkv as in `attention`.
+        Returns out bf16 [n_prefix * n, ldo] in the same order.  stream=True: the key-streaming kernel (d_h = 64)."""
+        dim = heads * d_h
+        for name, t in (("qkv", qkv), ("q", q), ("out", out)):
+            if t is not None and (t.device.type != "cuda" or t.dim() != 2 or t.dtype != torch.bfloat16 or t.stride(1) != 1 or t.stride(0) < t.shape[1]):
+                raise ValueError(f"{name} must be a row-major 2-D bf16 device tensor")
+        if qkv.shape[1] != 3 * dim or qkv.stride(0) != 3 * dim or q.shape[1] != dim or q.stride(0) != dim:
+            raise ValueError(f"qkv must be [rows, {3 * dim}] and q [n_prefix * n, {dim}], densely packed (the kernels' row strides)")
+        if qkv.shape[0] < ssp2_rows(n, tokens, group) or q.shape[0] < n_prefix * n:
+            raise ValueError(f"qkv [{tuple(qkv.shape)}] / q [{tuple(q.shape)}] too small for n={n} tokens={tokens} n_prefix={n_prefix} group={group}")
+        if out is None:
+            out = torch.empty(n_prefix * n, dim, dtype=torch.bfloat16, device=qkv.device)
+        if out.shape[0] < n_prefix * n or out.shape[1] < dim:
+            raise ValueError(f"output [{tuple(out.shape)}] smaller than [{n_prefix * n}, {dim}]")
+        self._check(self.lib.ssp2_attention_prefix_bf16(C.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream), _ptr(qkv), n, tokens,
+                                                        heads, d_h, group, _ptr(q), _ptr(out), out.stride(0), int(n_prefix), int(bool(stream))))
         return out
 
     def layernorm(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, *, rows: Optional[int] = None,

@@ -48,7 +48,8 @@ class _PatchEmbed(nn.Module):
 
 class EngineViT(nn.Module):
     """timm-layout container (`.blocks[i].{norm1,attn.qkv,attn.proj,norm2,mlp.fc1,mlp.fc2}`, `.patch_embed.proj`,
-    `.cls_token`, `.pos_embed`, `.norm`, `.head`); `model(px)` returns logits computed by libssp2vit."""
+    `.cls_token`, `.pos_embed`, `.norm`, `.head`; distilled DeiT weights add timm's `.dist_token` and `.head_dist`); `model(px)`
+    returns logits computed by libssp2vit."""
 
     def __init__(self, w: Dict):
         super().__init__()
@@ -57,9 +58,13 @@ class EngineViT(nn.Module):
         self.patch_embed = _PatchEmbed(dim, int(w["patch"]))
         self.cls_token = nn.Parameter(torch.zeros(1, 1, dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, w["pos"].shape[1], dim))
+        if int(w.get("prefix_tokens", 1)) == 2:
+            self.dist_token = nn.Parameter(torch.zeros(1, 1, dim))
         self.blocks = nn.ModuleList([_EngineBlock(dim, heads, int(w[f"fc1_w.{i}"].shape[0]), eps) for i in range(depth)])
         self.norm = nn.LayerNorm(dim, eps=eps)
         self.head = nn.Linear(dim, int(w["classes"]))
+        if "head_dist_w" in w:
+            self.head_dist = nn.Linear(dim, int(w["classes"]))
         self.config = SimpleNamespace(hidden_size=dim, num_attention_heads=heads, num_labels=int(w["classes"]),
                                       image_size=int(w["img"]), patch_size=int(w["patch"]), layer_norm_eps=eps)
         self.ssp2_origin_layout = str(w.get("origin_layout") or w.get("layout") or "timm")     # where the weights came from (export writes it)
@@ -76,6 +81,10 @@ class EngineViT(nn.Module):
                 put(b.mlp.fc2.weight, w[f"fc2_w.{i}"]); put(b.mlp.fc2.bias, w[f"fc2_b.{i}"])
             put(self.norm.weight, w["lnf_g"]); put(self.norm.bias, w["lnf_b"])
             put(self.head.weight, w["head_w"]); put(self.head.bias, w["head_b"])
+            if hasattr(self, "dist_token"):
+                put(self.dist_token, w["dist"])
+            if hasattr(self, "head_dist"):
+                put(self.head_dist.weight, w["head_dist_w"]); put(self.head_dist.bias, w["head_dist_b"])
         for i, b in enumerate(self.blocks):              # a checkpoint saved after stage 2: those blocks have no attention
             if w.get(f"attn_absent.{i}"):
                 b.attn = _vp.TimmAttentionBypass()

@@ -12,6 +12,12 @@ Keys (all tensors fp32, CPU, contiguous; layer index ``i`` in ``0..depth-1``)::
     fc1_w.i [d_int_i,dim] fc1_b.i [d_int_i]
     fc2_w.i [dim,d_int_i] fc2_b.i [dim]
     lnf_g lnf_b [dim]    head_w [classes,dim]  head_b [classes]
+    prefix_tokens                                    1 (CLS), or 2 (CLS + distillation token: distilled DeiT); default 1
+    dist [1,1,dim]                                   the distillation token (prefix_tokens == 2)
+    head_dist_w [classes,dim]  head_dist_b [classes] the distillation head: logits = (head(CLS) + head_dist(DIST)) / 2
+
+N = patches + prefix_tokens: pos covers every token.  A model with two prefix tokens and no ``head_dist_w`` (HF
+``DeiTForImageClassification``) reads its head on CLS only.
 
 ``nn.Linear`` row-major ``[out,in]`` is kept as is: it is already the K-contiguous "B^T" layout
 the MFMA GEMM wants.  Anatomy adapters (``from_module``) accept the same three layouts the
@@ -57,11 +63,27 @@ VIT_CONFIGS = {
     "vit_base_patch16_384_d2": (384, 16, 768, 12, 3072, 2),
     "vit_small_patch8_224_d2": (224, 8, 384, 6, 1536, 2),
     "vit_tiny_patch16_512_d2": (512, 16, 192, 3, 768, 2),
+    # distilled DeiT (a distillation token behind CLS, logits = mean of the CLS and DIST heads: DISTILLED below) and test cuts of it;
+    # the 32-pixel test config has 4 patches + 2 = 6 tokens at d_h = 16
+    "deit_tiny_distilled_patch16_224": (224, 16, 192, 3, 768, 12),
+    "deit_small_distilled_patch16_224": (224, 16, 384, 6, 1536, 12),
+    "deit_base_distilled_patch16_224": (224, 16, 768, 12, 3072, 12),
+    "deit_base_distilled_patch16_384": (384, 16, 768, 12, 3072, 12),
+    "deit_small_distilled_patch16_224_d2": (224, 16, 384, 6, 1536, 2),
+    "deit_base_distilled_patch16_384_d2": (384, 16, 768, 12, 3072, 2),
+    "deit_test_distilled_patch16_32": (32, 16, 64, 4, 128, 4),
 }
+# VIT_CONFIGS entries with a distillation token and head (their entries stay (img, patch, dim, heads, d_int, depth))
+DISTILLED = frozenset(k for k in VIT_CONFIGS if k.startswith("deit_") and "_distilled_" in k)
+
+
+def prefix_tokens_of(name: str) -> int:
+    """Tokens in front of the patches of a VIT_CONFIGS model: 2 for the distilled DeiTs, else 1."""
+    return 2 if name in DISTILLED else 1
 
 
 def n_tokens(w: Dict) -> int:
-    return (int(w["img"]) // int(w["patch"])) ** 2 + 1
+    return (int(w["img"]) // int(w["patch"])) ** 2 + int(w.get("prefix_tokens", 1))
 
 
 def synthetic_weights(name: str = "vit_base_patch16_224", classes: int = 1000, seed: int = 0,
@@ -84,8 +106,11 @@ def synthetic_weights(name: str = "vit_base_patch16_224", classes: int = 1000, s
     def bias(n):
         return torch.randn(n, generator=g) * bias_std if bias_std > 0 else torch.zeros(n)
 
-    n_tok = (img // patch) ** 2 + 1
+    prefix = prefix_tokens_of(name)
+    n_tok = (img // patch) ** 2 + prefix
     w: Dict = dict(img=img, patch=patch, dim=dim, heads=heads, depth=depth, classes=classes, eps=eps)
+    if prefix != 1:
+        w["prefix_tokens"] = prefix
     w["patch_w"] = tn(dim, 3, patch, patch)
     w["patch_b"] = bias(dim)
     w["cls"] = tn(1, 1, dim)
@@ -103,6 +128,9 @@ def synthetic_weights(name: str = "vit_base_patch16_224", classes: int = 1000, s
         w[f"fc2_w.{i}"] = tn(dim, inter); w[f"fc2_b.{i}"] = bias(dim)
     w["lnf_g"] = torch.ones(dim); w["lnf_b"] = torch.zeros(dim)
     w["head_w"] = tn(classes, dim); w["head_b"] = bias(classes)
+    if prefix == 2:
+        w["dist"] = tn(1, 1, dim)
+        w["head_dist_w"] = tn(classes, dim); w["head_dist_b"] = bias(classes)
     return w
 
 
@@ -140,15 +168,96 @@ def score_site_for(layout: str) -> str:
     return "pre_gelu" if layout == "timm" else "post_gelu"
 
 
+def _check_timm_token_layout(model) -> int:
+    """Prefix tokens of a timm-layout module (1, or 2 with `dist_token`), after refusing every layout the engine cannot represent:
+    register tokens, position embeddings without the prefix rows (`no_embed_class`), a pooled head (`global_pool` other than
+    'token', a `fc_norm` that is not Identity) and more than two prefix tokens."""
+    if getattr(model, "reg_token", None) is not None or int(getattr(model, "num_reg_tokens", 0) or 0) > 0:
+        raise ValueError("reg_token: register tokens are not supported (the engine's sequence is CLS [+ DIST] + patches)")
+    if getattr(model, "no_embed_class", False):
+        raise ValueError("no_embed_class: position embeddings without the prefix tokens' rows are not supported")
+    pool = getattr(model, "global_pool", "token")
+    if pool not in ("token", None):
+        raise ValueError(f"global_pool={pool!r}: only the token head ('token': the head reads CLS [+ DIST]) is supported")
+    fcn = getattr(model, "fc_norm", None)
+    if fcn is not None and not isinstance(fcn, torch.nn.Identity):
+        raise ValueError(f"fc_norm: a {type(fcn).__name__} in front of the head is not supported (only Identity)")
+    prefix = 1 + (getattr(model, "dist_token", None) is not None)
+    npt = getattr(model, "num_prefix_tokens", None)
+    if npt is not None and int(npt) != prefix:
+        raise ValueError(f"num_prefix_tokens={int(npt)}: the engine supports CLS or CLS + dist_token (1 or 2 prefix tokens)")
+    return prefix
+
+
+def _hf_base(model):
+    """The HF backbone (ViTModel / DeiTModel) of a classification model, or the model itself."""
+    for name in ("vit", "deit"):
+        b = getattr(model, name, None)
+        if b is not None:
+            return b
+    b = getattr(model, "base_model", None)
+    return b if b is not None and b is not model and hasattr(b, "embeddings") else model
+
+
+def _hf_heads(model, w: Dict) -> None:
+    """HF classifiers: `classifier` (ViT, DeiTForImageClassification: the CLS row) or the teacher model's `cls_classifier` +
+    `distillation_classifier` (logits = their mean, DeiTForImageClassificationWithTeacher)."""
+    if hasattr(model, "cls_classifier") and hasattr(model, "distillation_classifier"):
+        w["head_w"], w["head_b"] = _f32(model.cls_classifier.weight), _bias_or_zeros(model.cls_classifier)
+        w["head_dist_w"], w["head_dist_b"] = _f32(model.distillation_classifier.weight), _bias_or_zeros(model.distillation_classifier)
+    elif isinstance(getattr(model, "classifier", None), torch.nn.Linear):
+        w["head_w"], w["head_b"] = _f32(model.classifier.weight), _bias_or_zeros(model.classifier)
+    else:
+        raise AttributeError("classifier: the HF model has no Linear classification head — the search evaluates top-1")
+
+
+def _hf_embeddings(emb, w: Dict) -> None:
+    if getattr(emb, "register_tokens", None) is not None:
+        raise ValueError("register_tokens: register tokens are not supported")
+    w["cls"], w["pos"] = _f32(emb.cls_token), _f32(emb.position_embeddings)
+    if getattr(emb, "distillation_token", None) is not None:
+        w["dist"] = _f32(emb.distillation_token)
+        w["prefix_tokens"] = 2
+
+
+def _side_of(w: Dict) -> int:
+    """Patches per side from the position embedding (patches + prefix tokens rows); a count that is no square plus the prefix (position
+    embeddings without the prefix rows, extra tokens) is refused rather than misread."""
+    prefix = int(w.get("prefix_tokens", 1))
+    n_tok = int(w["pos"].shape[1])
+    side = int(round(math.sqrt(max(n_tok - prefix, 0))))
+    if side < 1 or side * side + prefix != n_tok:
+        raise ValueError(f"pos_embed: {n_tok} rows are not {prefix} prefix token(s) + a square number of patches "
+                         "(no_embed_class or extra tokens are not supported)")
+    return side
+
+
+def token_layout(model) -> tuple:
+    """(prefix_tokens, dist_head) of a live module, read from its attributes without copying a weight (the engine cache keys on it)."""
+    if detect_layout(model) == "timm":
+        dist = getattr(model, "dist_token", None) is not None
+        return (2 if dist else 1, int(dist and getattr(model, "head_dist", None) is not None))
+    emb = getattr(_hf_base(model), "embeddings", None)
+    dist = getattr(emb, "distillation_token", None) is not None
+    return (2 if dist else 1, int(dist and hasattr(model, "distillation_classifier")))
+
+
 def from_module(model) -> Dict:
-    """Extract the flat dictionary from a live module (weights are copied, the module is untouched)."""
+    """Extract the flat dictionary from a live module (weights are copied, the module is untouched).  Distilled DeiT (timm
+    `dist_token` + `head_dist`; HF `distillation_token` + `cls_classifier` / `distillation_classifier`, or a CLS-only `classifier`)
+    gives prefix_tokens = 2; layouts the engine cannot represent raise ValueError naming the attribute."""
     layout = detect_layout(model)
     w: Dict = {}
     if layout == "timm":
+        prefix = _check_timm_token_layout(model)
         pe = model.patch_embed.proj
         blocks = list(model.blocks)
         w["patch_w"], w["patch_b"] = _f32(pe.weight), _f32(pe.bias)
         w["cls"], w["pos"] = _f32(model.cls_token), _f32(model.pos_embed)
+        if prefix == 2:
+            w["dist"], w["prefix_tokens"] = _f32(model.dist_token), 2
+            if getattr(model, "head_dist", None) is not None:
+                w["head_dist_w"], w["head_dist_b"] = _f32(model.head_dist.weight), _bias_or_zeros(model.head_dist)
         for i, b in enumerate(blocks):
             w[f"ln1_g.{i}"], w[f"ln1_b.{i}"] = _f32(b.norm1.weight), _f32(b.norm1.bias)
             attn = getattr(b, "attn", None)
@@ -161,7 +270,7 @@ def from_module(model) -> Dict:
             w[f"fc1_w.{i}"], w[f"fc1_b.{i}"] = _f32(b.mlp.fc1.weight), _f32(b.mlp.fc1.bias)
             w[f"fc2_w.{i}"], w[f"fc2_b.{i}"] = _f32(b.mlp.fc2.weight), _f32(b.mlp.fc2.bias)
         w["lnf_g"], w["lnf_b"] = _f32(model.norm.weight), _f32(model.norm.bias)
-        w["head_w"], w["head_b"] = _f32(model.head.weight), _f32(model.head.bias)
+        w["head_w"], w["head_b"] = _f32(model.head.weight), _bias_or_zeros(model.head)
         eps = float(model.norm.eps)
         # the head count lives on the attention modules; block 0 may already be a bypass (the heuristic prunes it
         # first), so take it from the first block that still has one, then from a config object
@@ -170,12 +279,12 @@ def from_module(model) -> Dict:
             heads = getattr(getattr(model, "config", None), "num_attention_heads", None)
             heads = None if heads is None else int(heads)
     elif layout == "hf":
-        vit = model.vit if hasattr(model, "vit") else model
+        vit = _hf_base(model)
         emb = vit.embeddings
         pe = emb.patch_embeddings.projection
         layers = list(vit.encoder.layer)
         w["patch_w"], w["patch_b"] = _f32(pe.weight), _f32(pe.bias)
-        w["cls"], w["pos"] = _f32(emb.cls_token), _f32(emb.position_embeddings)
+        _hf_embeddings(emb, w)
         for i, l in enumerate(layers):
             w[f"ln1_g.{i}"], w[f"ln1_b.{i}"] = _f32(l.layernorm_before.weight), _f32(l.layernorm_before.bias)
             att = getattr(l, "attention", None)
@@ -190,16 +299,16 @@ def from_module(model) -> Dict:
             w[f"fc1_w.{i}"], w[f"fc1_b.{i}"] = _f32(l.intermediate.dense.weight), _f32(l.intermediate.dense.bias)
             w[f"fc2_w.{i}"], w[f"fc2_b.{i}"] = _f32(l.output.dense.weight), _f32(l.output.dense.bias)
         w["lnf_g"], w["lnf_b"] = _f32(vit.layernorm.weight), _f32(vit.layernorm.bias)
-        w["head_w"], w["head_b"] = _f32(model.classifier.weight), _f32(model.classifier.bias)
+        _hf_heads(model, w)
         eps = float(vit.layernorm.eps)
         heads = int(getattr(model.config, "num_attention_heads"))
     else:  # hf5: vit.layers[i].{layernorm_before, attention.{q,k,v,o}_proj, layernorm_after, mlp.fc1/fc2}
-        vit = model.vit if hasattr(model, "vit") else model
+        vit = _hf_base(model)
         emb = vit.embeddings
         pe = emb.patch_embeddings.projection
         layers = list(getattr(vit, "layers", None) or vit.encoder.layers)
         w["patch_w"], w["patch_b"] = _f32(pe.weight), _f32(pe.bias)
-        w["cls"], w["pos"] = _f32(emb.cls_token), _f32(emb.position_embeddings)
+        _hf_embeddings(emb, w)
         for i, l in enumerate(layers):
             w[f"ln1_g.{i}"], w[f"ln1_b.{i}"] = _f32(l.layernorm_before.weight), _f32(l.layernorm_before.bias)
             a = l.attention
@@ -213,14 +322,13 @@ def from_module(model) -> Dict:
             w[f"fc1_w.{i}"], w[f"fc1_b.{i}"] = _f32(l.mlp.fc1.weight), _f32(l.mlp.fc1.bias)
             w[f"fc2_w.{i}"], w[f"fc2_b.{i}"] = _f32(l.mlp.fc2.weight), _f32(l.mlp.fc2.bias)
         w["lnf_g"], w["lnf_b"] = _f32(vit.layernorm.weight), _f32(vit.layernorm.bias)
-        w["head_w"], w["head_b"] = _f32(model.classifier.weight), _f32(model.classifier.bias)
+        _hf_heads(model, w)
         eps = float(vit.layernorm.eps)
         heads = int(getattr(model.config, "num_attention_heads"))
 
     dim = int(w["patch_w"].shape[0])
     patch = int(w["patch_w"].shape[-1])
-    n_tok = int(w["pos"].shape[1])
-    side = int(round(math.sqrt(n_tok - 1)))
+    side = _side_of(w)
     depth = sum(1 for k in w if k.startswith("ln1_g."))
     if heads is None:
         if depth and all(w.get(f"attn_absent.{i}") for i in range(depth)):
@@ -258,8 +366,13 @@ def from_state_dict(sd: Dict[str, torch.Tensor], config: Optional[Dict] = None, 
     absent = set(int(i) for i in meta.get("attention_removed_blocks", []))
     if has("patch_embed.proj.weight"):                                   # ---- timm
         layout = "timm"
+        for k, what in (("reg_token", "register tokens"), ("fc_norm.weight", "a LayerNorm in front of the head (fc_norm: pooled head)")):
+            if has(k):
+                raise ValueError(f"{k.split('.')[0]}: {what} not supported")
         w["patch_w"], w["patch_b"] = f("patch_embed.proj.weight"), f("patch_embed.proj.bias")
         w["cls"], w["pos"] = f("cls_token"), f("pos_embed")
+        if has("dist_token"):                                            # distilled DeiT: CLS + DIST, two heads averaged
+            w["dist"], w["prefix_tokens"] = f("dist_token"), 2
         dim = int(w["patch_w"].shape[0])
         i = 0
         while has(f"blocks.{i}.norm1.weight"):
@@ -278,14 +391,22 @@ def from_state_dict(sd: Dict[str, torch.Tensor], config: Optional[Dict] = None, 
         if not has("head.weight"):
             raise AttributeError("Unsupported ViT checkpoint: no classification head (head.weight) — the search evaluates top-1")
         w["head_w"], w["head_b"] = f("head.weight"), opt("head.bias", int(sd["head.weight"].shape[0]))
+        if has("head_dist.weight"):
+            if not has("dist_token"):
+                raise ValueError("head_dist: a distillation head without a dist_token")
+            w["head_dist_w"], w["head_dist_b"] = f("head_dist.weight"), opt("head_dist.bias", int(sd["head_dist.weight"].shape[0]))
         eps = float(config.get("layer_norm_eps", meta.get("layer_norm_eps", 1e-6)))
     else:
-        pre = "vit." if any(k.startswith("vit.") for k in sd) else ""
+        pre = next((p for p in ("vit.", "deit.") if any(k.startswith(p) for k in sd)), "")
         emb = pre + "embeddings."
         if not has(emb + "patch_embeddings.projection.weight"):
             raise AttributeError("Unsupported ViT checkpoint: neither timm (patch_embed.proj) nor HF (embeddings.patch_embeddings) keys")
+        if has(emb + "register_tokens"):
+            raise ValueError("register_tokens: register tokens are not supported")
         w["patch_w"], w["patch_b"] = f(emb + "patch_embeddings.projection.weight"), f(emb + "patch_embeddings.projection.bias")
         w["cls"], w["pos"] = f(emb + "cls_token"), f(emb + "position_embeddings")
+        if has(emb + "distillation_token"):                              # DeiT: CLS + DIST
+            w["dist"], w["prefix_tokens"] = f(emb + "distillation_token"), 2
         dim = int(w["patch_w"].shape[0])
         if has(pre + "encoder.layer.0.layernorm_before.weight"):        # ---- transformers < 5
             layout, base = "hf", pre + "encoder.layer."
@@ -314,9 +435,16 @@ def from_state_dict(sd: Dict[str, torch.Tensor], config: Optional[Dict] = None, 
             w[f"fc2_w.{i}"], w[f"fc2_b.{i}"] = f(fc2 + ".weight"), f(fc2 + ".bias")
             i += 1
         w["lnf_g"], w["lnf_b"] = f(pre + "layernorm.weight"), f(pre + "layernorm.bias")
-        if not has("classifier.weight"):
+        if has("cls_classifier.weight") and has("distillation_classifier.weight"):      # DeiTForImageClassificationWithTeacher
+            w["head_w"], w["head_b"] = f("cls_classifier.weight"), opt("cls_classifier.bias", int(sd["cls_classifier.weight"].shape[0]))
+            w["head_dist_w"] = f("distillation_classifier.weight")
+            w["head_dist_b"] = opt("distillation_classifier.bias", int(sd["distillation_classifier.weight"].shape[0]))
+        elif not has("classifier.weight"):
             raise AttributeError("Unsupported ViT checkpoint: no classification head (classifier.weight; a bare ViTModel?) — the search evaluates top-1")
-        w["head_w"], w["head_b"] = f("classifier.weight"), opt("classifier.bias", int(sd["classifier.weight"].shape[0]))
+        else:
+            w["head_w"], w["head_b"] = f("classifier.weight"), opt("classifier.bias", int(sd["classifier.weight"].shape[0]))
+        if "head_dist_w" in w and "dist" not in w:
+            raise ValueError("distillation_classifier: a distillation head without a distillation_token")
         eps = float(config.get("layer_norm_eps", meta.get("layer_norm_eps", 1e-12)))
     depth = i
     if depth == 0:
@@ -333,7 +461,7 @@ def from_state_dict(sd: Dict[str, torch.Tensor], config: Optional[Dict] = None, 
             w[f"qkv_w.{b}"] = torch.zeros(3 * dim, dim); w[f"qkv_b.{b}"] = torch.zeros(3 * dim)
             w[f"proj_w.{b}"] = torch.zeros(dim, dim); w[f"proj_b.{b}"] = torch.zeros(dim)
     patch = int(w["patch_w"].shape[-1])
-    side = int(round(math.sqrt(int(w["pos"].shape[1]) - 1)))
+    side = _side_of(w)
     w.update(img=side * patch, patch=patch, dim=dim, heads=int(heads), depth=depth, classes=int(w["head_w"].shape[0]),
              eps=eps, layout=layout)
     # A checkpoint this build exported says where it came from (pruning_meta.json): an HF-origin model re-saved in the timm key

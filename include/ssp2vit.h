@@ -39,6 +39,9 @@ enum {
   SSP2_T_LN1_G, SSP2_T_LN1_B, SSP2_T_QKV_W, SSP2_T_QKV_B, SSP2_T_PROJ_W, SSP2_T_PROJ_B,
   SSP2_T_LN2_G, SSP2_T_LN2_B, SSP2_T_FC1_W, SSP2_T_FC1_B, SSP2_T_FC2_W, SSP2_T_FC2_B,
   SSP2_T_LNF_G, SSP2_T_LNF_B, SSP2_T_HEAD_W, SSP2_T_HEAD_B,
+  /* distilled models only (ssp2_create_ext with prefix_tokens = 2 / dist_head = 1; any other engine refuses them, SSP2_EINVAL):
+   * the distillation token [dim] and the distillation head [classes, dim] + [classes] */
+  SSP2_T_DIST, SSP2_T_HEAD_DIST_W, SSP2_T_HEAD_DIST_B,
   SSP2_T_COUNT
 };
 
@@ -57,7 +60,7 @@ typedef struct ssp2_engine* ssp2_handle;
 
 typedef struct {
   int32_t img;          /* input resolution (square)                               */
-  int32_t patch;        /* patch size; tokens N = (img/patch)^2 + 1                */
+  int32_t patch;        /* patch size; tokens N = (img/patch)^2 + 1 (+ prefix_tokens instead of 1: ssp2_create_ext) */
   int32_t dim;          /* hidden size, multiple of 64                             */
   int32_t heads;        /* dim/heads in {16, 64, 80}; tokens = (img/patch)^2 + 1 must fall into an instantiated key-tile count:
                          * d_h 64: up to 288 tokens (ViT-Ti/S/B/L at /16 and /32 up to 256 pixels; ViT-L/14); d_h 80: 257..288 (ViT-H/14);
@@ -81,6 +84,20 @@ int ssp2_create(const ssp2_vit_desc* desc, ssp2_handle* out);
  * environment's default, as ssp2_create) or the option's value (SSP2_OPT_ATTN_STREAM = 1 lets a > 288-token d_h 64 model be created
  * without touching the environment).  opt == NULL is ssp2_create. */
 int ssp2_create_opts(const ssp2_vit_desc* desc, const int32_t* opt, ssp2_handle* out);
+/* Token layout beyond the plain ViT's (one CLS token in front of the patches, one head on the CLS row): distilled DeiT
+ * (deit_*_distilled_*: a CLS and a distillation token, tokens = patches + 2; in eval mode logits = (head(norm(x)[:, 0]) +
+ * head_dist(norm(x)[:, 1])) / 2) and HF DeiTForImageClassification (the same two tokens, a head on CLS only).
+ *   prefix_tokens  1 or 2: tokens in front of the patches.  Row 0 = cls + pos[0], row 1 = dist + pos[1] (SSP2_T_DIST); patch q is
+ *                  token prefix_tokens + q.  pos (SSP2_T_POS) covers all tokens.
+ *   dist_head      1: the logits are 0.5f * bf16(head(LN(row 0)) + head_dist(LN(row 1))) (SSP2_T_HEAD_DIST_W / _B), needs
+ *                  prefix_tokens == 2; 0: the head reads row 0 only.
+ * ssp2_tail* then carry the rows the head reads (2 with dist_head, else 1) through the last block; ssp2_head gathers them. */
+typedef struct {
+  int32_t prefix_tokens;
+  int32_t dist_head;
+} ssp2_vit_ext;
+/* ssp2_create_opts with a token layout; ext == NULL is ssp2_create_opts (and {1, 0} gives the same engine) */
+int ssp2_create_ext(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_vit_ext* ext, ssp2_handle* out);
 int ssp2_destroy(ssp2_handle h);
 int ssp2_set_stream(ssp2_handle h, void* hip_stream);
 /* Cap the grids of the handle's persistent kernels (large-tile GEMMs, d_h = 64 attention) at n_cu workgroups (<= 0 or
@@ -295,6 +312,12 @@ int ssp2_attention_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int to
  * fp32.  Every argument is checked before the device is touched. */
 int ssp2_attention_stream_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
                                const uint16_t* q_cls_dev, uint16_t* out_dev, int ldo);
+/* The prefix-query attention of the evaluation tail on its own: the CLS-only form of ssp2_attention_bf16 (resident kernels; stream != 0:
+ * the key-streaming kernel of ssp2_attention_stream_bf16, d_h = 64 only) for n_prefix = 1 or 2 queries per image.  q_dev bf16 holds
+ * the queries prefix-major, [n_prefix][n][heads * d_h] densely packed; out_dev bf16 [n_prefix][n][ldo] receives them in the same order
+ * (prefix row t of image i at out_dev + (t * n + i) * ldo).  Every argument is checked before the device is touched. */
+int ssp2_attention_prefix_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
+                               const uint16_t* q_dev, uint16_t* out_dev, int ldo, int n_prefix, int stream);
 
 /* LayerNorm over the last dim on its own, on caller-owned device buffers: the forward's launch (one instantiation per 256-wide
  * step of D, the unpredicated form where D = 256 * MAXV, the reverse walk from 4096 rows on when rev = 1).
