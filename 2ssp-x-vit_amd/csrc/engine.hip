@@ -1621,6 +1621,63 @@ int ssp2_linear_bf16(void* hip_stream, int epilogue, const uint16_t* a_dev, int 
   }
 }
 
+// The fp8 projection operator on its own: the forward's launch_gemm256<EPI, SCORE, true> (QKV, fc1 with its score sites, the
+// residual projections) on caller-owned e4m3 operands.  Every argument is checked before the device is touched.
+int ssp2_linear_e4m3(void* hip_stream, int epilogue, const uint8_t* a_dev, int lda, const float* ascale_dev, float ascale_const,
+                     const uint8_t* w_dev, int ldw, const float* wscale_dev, const float* bias_dev, int M, int N, int K,
+                     void* out_dev, int ldo, float* x_dev, const float* xin_dev, int ldx,
+                     int score_site, int tokens, int group, int n_img, float* slab_dev, int slab_ld, int rev) {
+  if (!a_dev || !w_dev || !bias_dev) return fail(SSP2_EINVAL, "linear_e4m3: null operand");
+  if (rev < 0 || rev > 1) return fail(SSP2_EINVAL, "linear_e4m3: rev=%d", rev);
+  if (!wscale_dev) return fail(SSP2_EINVAL, "linear_e4m3: the weight rows' scales (wscale) are required");
+  if (M <= 0 || N <= 0 || K <= 0 || (K % 128) || (N % 64)) return fail(SSP2_EINVAL, "linear_e4m3: M=%d N=%d K=%d (K multiple of 128, N multiple of 64)", M, N, K);
+  if (lda < K || ldw < K || (lda % 16) || (ldw % 16)) return fail(SSP2_EINVAL, "linear_e4m3: lda=%d ldw=%d must be >= K and multiples of 16", lda, ldw);
+  if (!std::isfinite(ascale_const) || ascale_const < 0.f) return fail(SSP2_EINVAL, "linear_e4m3: ascale_const=%g", ascale_const);
+  if (ascale_dev && ascale_const != 0.f) return fail(SSP2_EINVAL, "linear_e4m3: per-row ascale and ascale_const are exclusive");
+  if (score_site < 0 || score_site > 2 || (score_site && epilogue != SSP2_EPI_GELU)) return fail(SSP2_EINVAL, "linear_e4m3: score_site=%d (1 / 2 with the GELU epilogue only)", score_site);
+  if (score_site) {
+    if (tokens < GEMM_BM) return fail(SSP2_EINVAL, "linear_e4m3: the scoring epilogue needs tokens >= %d (tokens=%d)", GEMM_BM, tokens);
+    if (!slab_dev || slab_ld <= 0 || slab_ld > N) return fail(SSP2_EINVAL, "linear_e4m3: slab / slab_ld=%d (1..N)", slab_ld);
+    if (group < 0 || n_img <= 0) return fail(SSP2_EINVAL, "linear_e4m3: group=%d n_img=%d", group, n_img);
+    if (total_rows(make_rowmap(tokens, n_img, group), n_img) > M)
+      return fail(SSP2_EINVAL, "linear_e4m3: %d images of %d tokens in groups of %d exceed M=%d rows", n_img, tokens, group, M);
+  }
+  ssp2_engine e;
+  e.stream = (hipStream_t)hip_stream; e.n_cu = op_cu_count(); e.dev = cur_device();
+  { const char* v = getenv("SSP2_NT_STORES"); e.opt[SSP2_OPT_NT_STORES] = (v && *v) ? atoi(v) : 1; }      // the forward's default store policy
+  e.opt[SSP2_OPT_ZIGZAG] = 1; e.zig = rev;           // the forward alternates the tile walk: next_dir() hands the launch this direction
+  GemmArgs g{};
+  g.A = (const bf16*)a_dev; g.lda = lda; g.W = (const bf16*)w_dev; g.ldw = ldw; g.bias = bias_dev;
+  g.wscale = wscale_dev; g.ascale = ascale_dev; g.ascale_const = ascale_const;
+  g.M = M; g.N = N; g.K = K;
+  g.out = (bf16*)out_dev; g.ldo = ldo; g.x = x_dev; g.xin = xin_dev; g.ldx = ldx;
+  switch (epilogue) {
+    case SSP2_EPI_BF16:
+      if (!out_dev || ldo < N || (ldo % 8)) return fail(SSP2_EINVAL, "linear_e4m3: out / ldo");
+      return launch_gemm256<EPI_BF16, 0, true>(&e, g, -2);
+    case SSP2_EPI_GELU:      // e4m3 bytes out, ldo in bytes
+      if (!out_dev || ldo < N || (ldo % 16)) return fail(SSP2_EINVAL, "linear_e4m3: out / ldo (bytes, a multiple of 16)");
+      if (!score_site) return launch_gemm256<EPI_FC1, 0, true>(&e, g, -2);
+      g.score_site = score_site; g.tokens = tokens; g.slab = slab_dev; g.slab_ld = slab_ld; g.n_img = n_img;
+      { const RowMap rm = make_rowmap(tokens, n_img, group); g.group = rm.group; g.mpad = rm.mpad; }
+      return score_site == 1 ? launch_gemm256<EPI_FC1, 1, true>(&e, g, -2) : launch_gemm256<EPI_FC1, 2, true>(&e, g, -2);
+    case SSP2_EPI_RESID:
+      if (!x_dev || ldx < N || (ldx % 4)) return fail(SSP2_EINVAL, "linear_e4m3: x / ldx");
+      return launch_gemm256<EPI_RESID, 0, true>(&e, g, -2);
+    default: return fail(SSP2_EINVAL, "unknown epilogue %d", epilogue);
+  }
+}
+
+// The weight quantiser on its own: what quantise_mat launches (quant_rows_e4m3_kernel), on caller-owned buffers.
+int ssp2_quantise_rows_e4m3(void* hip_stream, const uint16_t* w_dev, int ld, int rows, int cols, int rows_pad, uint8_t* w8_dev, int ld8, float* scale_dev) {
+  if (!w_dev || !w8_dev || !scale_dev) return fail(SSP2_EINVAL, "quantise_rows_e4m3: null buffer");
+  if (rows <= 0 || cols <= 0 || ld < cols || rows_pad < rows) return fail(SSP2_EINVAL, "quantise_rows_e4m3: rows=%d cols=%d ld=%d rows_pad=%d", rows, cols, ld, rows_pad);
+  if (ld8 < cols || ld8 % 16) return fail(SSP2_EINVAL, "quantise_rows_e4m3: ld8=%d (>= cols %d, a multiple of 16)", ld8, cols);
+  hipLaunchKernelGGL(quant_rows_e4m3_kernel, dim3((rows_pad + 3) / 4), dim3(256), 0, (hipStream_t)hip_stream, (const bf16*)w_dev, ld, w8_dev, ld8, scale_dev, rows, cols, rows_pad);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // Multi-head attention on its own, on caller-owned buffers: a temporary engine with the forward's buffers pointed at the caller's,
 // then launch_attn — the routing and the instantiations of the forward (persistent / one-item kernel, LIVE, CLS-only tail).  Every
 // argument is checked before the device is touched.

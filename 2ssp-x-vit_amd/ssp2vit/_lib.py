@@ -19,7 +19,7 @@ ABI_VERSION = 7                                         # SSP2_ABI_VERSION of in
 # every symbol include/ssp2vit.h declares
 SYMBOLS = [
     "ssp2_abi_version", "ssp2_last_error", "ssp2_create", "ssp2_destroy", "ssp2_set_stream", "ssp2_load_tensor",
-    "ssp2_load_tensor_dev", "ssp2_load_tensors_dev", "ssp2_linear_bf16", "ssp2_attention_bf16", "ssp2_layernorm", "ssp2_query", "ssp2_restore_attention", "ssp2_clone_weights",
+    "ssp2_load_tensor_dev", "ssp2_load_tensors_dev", "ssp2_linear_bf16", "ssp2_linear_e4m3", "ssp2_quantise_rows_e4m3", "ssp2_attention_bf16", "ssp2_layernorm", "ssp2_query", "ssp2_restore_attention", "ssp2_clone_weights",
     "ssp2_prune_ffn_into", "ssp2_set_precision", "ssp2_set_cu_limit", "ssp2_set_option", "ssp2_get_option", "ssp2_profile_query",
     "ssp2_embed", "ssp2_layers", "ssp2_layers_from", "ssp2_layers_prefix", "ssp2_head", "ssp2_tail", "ssp2_tail_slots", "ssp2_tail_group", "ssp2_prune_ffn", "ssp2_drop_attention", "ssp2_d_int", "ssp2_act_l2_accum", "ssp2_profile_begin", "ssp2_profile_end",
     "ssp2_tokens", "ssp2_rows", "ssp2_workspace_bytes", "ssp2_preproc_create", "ssp2_preproc_run", "ssp2_preproc_destroy",
@@ -229,6 +229,8 @@ def load(build_if_missing: bool = True, variant: Optional[str] = None) -> C.CDLL
     lib.ssp2_load_tensor_dev.argtypes = [vp, i32, i32, vp, C.c_size_t]
     lib.ssp2_load_tensors_dev.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp), C.POINTER(C.c_size_t)]
     lib.ssp2_linear_bf16.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, vp, i32, i32]
+    lib.ssp2_linear_e4m3.argtypes = [vp, i32, vp, i32, vp, C.c_float, vp, i32, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32]
+    lib.ssp2_quantise_rows_e4m3.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp]
     lib.ssp2_attention_bf16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, C.c_float, vp, i32, i32, i32]
     lib.ssp2_attention_stream_bf16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32]
     lib.ssp2_attention_prefix_bf16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32]

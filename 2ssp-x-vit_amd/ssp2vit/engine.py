@@ -440,6 +440,82 @@ class VitEngine:
                                         {"auto": 0, "small": 1, "big": 2}[kernel]))
         return x if epi == 1 else out
 
+    def quantise_e4m3(self, w: torch.Tensor, *, rows_pad: Optional[int] = None, ld8: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The fp8 mode's weight quantiser on its own (ssp2_quantise_rows_e4m3, what ssp2_set_precision runs): w [rows, cols] (any float
+        dtype, rounded to bf16).  Returns (uint8 [rows_pad, ld8] e4m3 bytes, f32 [rows_pad] row scales amax / 448); rows_pad defaults to
+        ceil256(rows), ld8 to ceil128(cols) — the engine's weight images.  Pad rows and columns are zero bytes, pad scales 1."""
+        rows, cols = w.shape
+        rows_pad = (rows + 255) // 256 * 256 if rows_pad is None else int(rows_pad)
+        ld8 = (cols + 127) // 128 * 128 if ld8 is None else int(ld8)
+        wb = w.to(self.device, torch.bfloat16).contiguous()
+        w8 = torch.empty(rows_pad, ld8, dtype=torch.uint8, device=self.device)
+        sc = torch.empty(rows_pad, dtype=torch.float32, device=self.device)
+        self._check(self.lib.ssp2_quantise_rows_e4m3(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), _ptr(wb), cols, rows,
+                                                     cols, rows_pad, _ptr(w8), ld8, _ptr(sc)))
+        return w8, sc
+
+    def linear_e4m3(self, a8: torch.Tensor, w8: torch.Tensor, wscale: torch.Tensor, bias: Optional[torch.Tensor], epilogue: str = "bf16", *,
+                    rows: Optional[int] = None, ascale: Optional[torch.Tensor] = None, ascale_const: float = 0.0,
+                    out: Optional[torch.Tensor] = None, x: Optional[torch.Tensor] = None, xin: Optional[torch.Tensor] = None,
+                    score_site: int = 0, tokens: int = 0, group: int = 0, n_img: int = 0, slab_ld: Optional[int] = None,
+                    rev: int = 0):
+        """One fp8 projection of the forward on its own (ssp2_linear_e4m3): a8 uint8 e4m3 [>= rows, lda] (rows = a8.shape[0] by default,
+        lda = its row stride), w8 uint8 [N, K] e4m3 with K the contraction length (K % 128 == 0), wscale f32 [N], bias [N] or None (rounded
+        to bf16); W, wscale and bias are padded to 256 rows like `linear` does.  Activation scale per row from ascale (f32 [>= rows]),
+        or ascale_const, or 1.  epilogue "bf16" -> out bf16 [rows, >= N]; "resid" -> x (f32 [>= rows, ld]) = xin (default x) +
+        bf16(...), returned; "gelu" -> out uint8 [rows, >= N] e4m3 bytes, and with score_site 1 / 2 (tokens, group, n_img: the row
+        layout of ssp2_rows) the tuple (out, slab f32 [2 * ceil(rows / 256), 2, slab_ld]), slab_ld defaulting to N: entry t
+        covers rows 128 t .. 128 t + 127 (zeros past the last row).  rev: the walk direction of the tiles (the forward alternates them)."""
+        epi = {"bf16": 0, "resid": 1, "gelu": 2}[epilogue]
+        N, K = w8.shape
+        M = a8.shape[0] if rows is None else int(rows)
+        for name, t in (("a8", a8), ("w8", w8), ("out", out if epi == 2 else None)):
+            if t is not None and (t.device.type != "cuda" or t.dim() != 2 or t.dtype != torch.uint8 or t.stride(1) != 1):
+                raise ValueError(f"{name} must be a row-major 2-D uint8 (e4m3) device tensor")
+        if a8.shape[0] < M or a8.shape[1] < K:
+            raise ValueError(f"a8 [{tuple(a8.shape)}] smaller than [{M}, {K}]")
+        # the kernel reads M rows of a8 at its row stride, and per-row scales at a stride of 1
+        if ascale is not None and (ascale.device.type != "cuda" or ascale.dtype != torch.float32 or ascale.dim() != 1
+                                   or ascale.stride(0) != 1 or ascale.numel() < M):
+            raise ValueError(f"ascale must be a dense f32 device vector of >= {M} entries")
+        if wscale.numel() != N:
+            raise ValueError("wscale must hold one scale per weight row")
+        npad = (N + 255) // 256 * 256
+        wp = torch.zeros(npad, K, dtype=torch.uint8, device=self.device)
+        wp[:N].copy_(w8)
+        sp = torch.ones(npad, dtype=torch.float32, device=self.device)
+        sp[:N].copy_(wscale.reshape(-1))
+        bp = torch.zeros(npad, dtype=torch.float32, device=self.device)
+        if bias is not None:
+            bp[:N].copy_(bias.to(self.device, torch.bfloat16).float())
+        slab = None
+        if epi == 1:
+            for name, t in (("x", x), ("xin", xin)):
+                if t is not None and (t.device.type != "cuda" or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1
+                                      or t.shape[0] < M or t.shape[1] < N):
+                    raise ValueError(f"resid epilogue needs {name} as a row-major f32 device tensor of >= [{M}, {N}]")
+            if x is None or (xin is not None and xin.stride(0) != x.stride(0)):
+                raise ValueError("resid epilogue needs x, and xin at x's row stride (the kernel reads both at ldx)")
+            ldo, ldx = 0, x.stride(0)
+        else:
+            if out is None:
+                out = torch.empty(M, N, dtype=torch.uint8 if epi == 2 else torch.bfloat16, device=self.device)
+            if out.device.type != "cuda" or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < M or out.shape[1] < N \
+                    or out.dtype != (torch.uint8 if epi == 2 else torch.bfloat16):
+                raise ValueError(f"out must be a row-major {'uint8' if epi == 2 else 'bf16'} device tensor of >= [{M}, {N}]")
+            ldo, ldx = out.stride(0), 0
+            if score_site:
+                slab_ld = N if slab_ld is None else int(slab_ld)
+                slab = torch.full((2 * ((M + 255) // 256), 2, slab_ld), float("nan"), dtype=torch.float32, device=self.device)
+        self._check(self.lib.ssp2_linear_e4m3(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), epi, _ptr(a8), a8.stride(0),
+                                              _ptr(ascale), float(ascale_const), _ptr(wp), K, _ptr(sp), _ptr(bp), M, N, K,
+                                              _ptr(out) if epi != 1 else None, ldo, _ptr(x) if epi == 1 else None,
+                                              _ptr(xin) if epi == 1 else None, ldx, int(score_site), int(tokens), int(group), int(n_img),
+                                              _ptr(slab), slab_ld or 0, int(rev)))
+        if epi == 1:
+            return x
+        return (out, slab) if score_site else out
+
     def attention(self, qkv: torch.Tensor, n: int, tokens: int, heads: int, d_h: int, *, group: int = 0,
                   out: Optional[torch.Tensor] = None, out8: Optional[torch.Tensor] = None, out8_scale: float = 16.0,
                   sat: Optional[torch.Tensor] = None, q_cls: Optional[torch.Tensor] = None, persist: Optional[bool] = None,

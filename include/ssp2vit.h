@@ -290,6 +290,31 @@ enum { SSP2_EPI_BF16 = 0, SSP2_EPI_RESID = 1, SSP2_EPI_GELU = 2 };
 int ssp2_linear_bf16(void* hip_stream, int epilogue, const uint16_t* a_dev, int lda, const uint16_t* w_dev, int ldw,
                      const float* bias_dev, int M, int N, int K, uint16_t* out_dev, int ldo, float* x_dev, int ldx, int kernel);
 
+/* Additive (ABI stays 7): the fp8 mode's projection on its own — the 256 x 256 kernel on e4m3 operands (OCP fp8 bytes), the very launches of the
+ * forward's QKV, fc1 (+ score sites) and residual projections, on caller-owned device buffers:
+ *   a_dev e4m3 [M, lda] (K used; rows past M never read), w_dev e4m3 [ceil256(N), ldw] (rows past N: zero bytes),
+ *   wscale_dev / bias_dev f32 [ceil256(N)] (bias bf16-representable), lda, ldw >= K and multiples of 16, K % 128 == 0, N % 64 == 0.
+ *   Activation scale of row m: ascale_dev[m] (per-row, what the LayerNorm writes), else ascale_const (the e4m3 attention output's
+ *   1 / 16), else 1 — ascale_dev and a non-zero ascale_const are exclusive.  pre = fma(acc * ascale, wscale[n], bias[n]):
+ *   SSP2_EPI_BF16  out_dev bf16 [M, ldo] = bf16(pre)                                   QKV
+ *   SSP2_EPI_RESID x_dev[M, ldx] = xin[M, ldx] + float(bf16(pre)) (xin_dev NULL: x_dev)  out-projection / fc2
+ *   SSP2_EPI_GELU  out_dev e4m3 bytes [M, ldo] (ldo in bytes, % 16) = e4m3(bf16(gelu_erf(bf16(pre)))), saturating at +-448  fc1
+ *   score_site 1 / 2 (GELU only, tokens >= 128): also the stage-1 slab [2 * ceil(M / 256)][2][slab_ld] f32, slab_ld <= N (a 256-row tile
+ *   writes both of its 128-row entries, zeros where wholly past M) — per 128-row
+ *   tile and segment (the rows of the tile's first / second image in the layout (tokens, group, n_img) of ssp2_rows, which must fit
+ *   in M) the sum of squares of bf16(pre) (site 1) or of the bf16 GELU output (site 2).  rev: walk direction of the tiles (0 / 1; the forward
+ *   alternates them), the same bits either way.  Every argument is checked before the
+ *   device is touched. */
+int ssp2_linear_e4m3(void* hip_stream, int epilogue, const uint8_t* a_dev, int lda, const float* ascale_dev, float ascale_const,
+                     const uint8_t* w_dev, int ldw, const float* wscale_dev, const float* bias_dev, int M, int N, int K,
+                     void* out_dev, int ldo, float* x_dev, const float* xin_dev, int ldx,
+                     int score_site, int tokens, int group, int n_img, float* slab_dev, int slab_ld, int rev);
+/* Additive (ABI stays 7): the fp8 mode's weight quantiser on its own (what ssp2_set_precision runs per weight): row r < rows of the bf16 w_dev
+ * [rows, ld] gets scale_dev[r] = amax / 448 (1 for a zero row) and w8_dev[r, c] = e4m3(w * (1 / scale)), saturating, for c < cols;
+ * columns [cols, ld8) and rows [rows, rows_pad) are zero bytes with scale 1.  ld8 >= cols, a multiple of 16. */
+int ssp2_quantise_rows_e4m3(void* hip_stream, const uint16_t* w_dev, int ld, int rows, int cols, int rows_pad, uint8_t* w8_dev, int ld8,
+                            float* scale_dev);
+
 /* Multi-head self-attention on its own, on caller-owned device buffers: the kernel the forward launches for this geometry, with
  * its routing (persistent / one-item kernel, the compile-time-padding LIVE form, the CLS-only tail).
  *   qkv_dev bf16 [rows, 3 * dim] in the engine's [row][q | k | v][head][d_h] layout, dim = heads * d_h; rows = ssp2_rows of

@@ -297,6 +297,52 @@ def test_operator_entries_refuse_bad_arguments_before_touching_the_device():
     assert ssp2_rows(4, 197, 2) == 512 + 394 and ssp2_rows(3, 50, 1) == 2 * 128 + 50
 
 
+def test_fp8_operator_entries_refuse_bad_arguments_before_touching_the_device():
+    """ssp2_linear_e4m3 / ssp2_quantise_rows_e4m3 check every argument before the first HIP call: each bad call comes back SSP2_EINVAL
+    (-1) with a message; the valid baselines get past the checks and fail at the device (SSP2_EHIP, -2) — so a -1 is the check's."""
+    import ctypes as C
+    from ssp2vit import _lib
+    from ssp2vit.engine import VitEngine
+    lib = _lib.load()
+    P = C.c_void_p(4096)
+
+    def lin(epi=0, a=P, lda=768, asc=None, asc_c=0.0, w=P, ldw=768, wsc=P, bias=P, M=4096, N=2304, K=768, out=P, ldo=2304,
+            x=None, xin=None, ldx=0, site=0, tokens=0, group=0, n_img=0, slab=None, slab_ld=0, rev=0):
+        return lib.ssp2_linear_e4m3(None, epi, a, lda, asc, asc_c, w, ldw, wsc, bias, M, N, K, out, ldo, x, xin, ldx, site, tokens,
+                                    group, n_img, slab, slab_ld, rev)
+    gelu = dict(epi=2, N=3072, ldo=3072)
+    score = dict(gelu, site=1, tokens=197, n_img=20, slab=P, slab_ld=3072)
+    resid = dict(epi=1, N=768, out=None, ldo=0, x=P, ldx=768)
+    for ok in (dict(), dict(asc=P), dict(asc_c=1 / 16), gelu, score, dict(score, site=2, group=4, n_img=4), resid, dict(resid, xin=P), dict(rev=1)):
+        assert lin(**ok) == -2, ok
+    bad = [dict(a=None), dict(w=None), dict(bias=None), dict(wsc=None), dict(M=0), dict(N=0), dict(K=0), dict(K=704, lda=704, ldw=704),
+           dict(N=2336, ldo=2336), dict(lda=640), dict(lda=776), dict(ldw=640), dict(ldw=776), dict(asc=P, asc_c=1 / 16),
+           dict(asc_c=float("nan")), dict(asc_c=-1.0), dict(site=1), dict(gelu, site=3), dict(epi=3), dict(out=None), dict(ldo=2300),
+           dict(ldo=2308), dict(gelu, ldo=3080), dict(gelu, out=None), dict(score, tokens=127), dict(score, slab=None),
+           dict(score, slab_ld=0), dict(score, slab_ld=3136), dict(score, n_img=21), dict(score, group=4, n_img=20),
+           dict(score, group=-1), dict(score, n_img=0), dict(resid, x=None), dict(resid, ldx=764), dict(resid, ldx=770), dict(rev=2), dict(rev=-1)]
+    for kw in bad:
+        assert lin(**kw) == -1, kw
+        assert lib.ssp2_last_error(), kw
+
+    def quant(w=P, ld=768, rows=2304, cols=768, rows_pad=2304, w8=P, ld8=768, sc=P):
+        return lib.ssp2_quantise_rows_e4m3(None, w, ld, rows, cols, rows_pad, w8, ld8, sc)
+    assert quant(cols=1030, ld=1030, ld8=1152, rows_pad=2560) == -2
+    for kw in [dict(w=None), dict(w8=None), dict(sc=None), dict(rows=0), dict(cols=0), dict(ld=767), dict(rows_pad=2303),
+               dict(ld8=640), dict(ld8=776), dict(cols=1030, ld=1030, ld8=1040 - 8)]:
+        assert quant(**kw) == -1, kw
+        assert lib.ssp2_last_error(), kw
+
+    # the wrappers refuse host tensors and layouts the kernel does not read before any call (an engine object without a device)
+    eng = VitEngine.__new__(VitEngine)
+    eng.lib = lib
+    a8, w8 = torch.zeros(256, 128, dtype=torch.uint8), torch.zeros(64, 128, dtype=torch.uint8)
+    with pytest.raises(ValueError):
+        eng.linear_e4m3(a8, w8, torch.ones(64), None)
+    with pytest.raises(ValueError):
+        eng.linear_e4m3(a8.float(), w8, torch.ones(64), None)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
 def test_product_path_fails_loudly_without_gpu():
     from oracle.vit_modules import build_from_flat
