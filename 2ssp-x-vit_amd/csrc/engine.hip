@@ -86,6 +86,9 @@ struct Layer {
   float o8_scale = ATTN_OUT8_SCALE;   // fp8 mode: the attention output of this block is handed to the out-projection as e4m3(o * o8_scale)
   int* keep_dev = nullptr;     // ssp2_prune_ffn_into: the kept-neuron list on the device
 };
+// everything a block's attention half / MLP half reads has been loaded (the block loop and the tail ask before they launch)
+static inline bool attn_loaded(const Layer& L) { return L.ln_set[0] && L.ln_set[1] && L.qkv.w_set && L.qkv.b_set && L.proj.w_set && L.proj.b_set; }
+static inline bool mlp_loaded(const Layer& L) { return L.ln_set[2] && L.ln_set[3] && L.fc1.w_set && L.fc1.b_set && L.fc2.w_set && L.fc2.b_set; }
 
 struct ssp2_engine {
   ssp2_vit_desc d{};
@@ -343,6 +346,65 @@ static int launch_gemm_small(ssp2_engine* e, GemmArgs g, int klass) {
   return 0;
 }
 
+// How a weight matrix and an activation become the operand half of a launch: A, lda, W, ldw, bias, K, the e4m3 scales, M, N and
+// tiles_n.  What else a launch needs (out / ldo, x / xin / ldx, the scoring and fused-LayerNorm fields, out2, group_m) is set where it
+// is launched.  The kernels take e4m3 operands through the bf16 pointers of GemmArgs, with lda / ldw / K / ldo counting BYTES: those
+// casts, and the byte-versus-element row arithmetic they bring (gemm_rows_from), are written here and nowhere else.
+struct ActOperand {        // the A operand: bf16 rows (p, ld in elements) or e4m3 bytes (p8, ld in bytes) with their dequantisation
+  const bf16* p; const uint8_t* p8; int ld;
+  const float* scale; float scale_const;     // e4m3: one scale per row, or (scale == nullptr) one for the whole operand (0 = 1)
+};
+static inline ActOperand act_bf16(const bf16* p, int ld) { return ActOperand{p, nullptr, ld, nullptr, 0.f}; }
+static inline ActOperand act_e4m3(const uint8_t* p8, int ld, const float* scale, float scale_const = 0.f) { return ActOperand{nullptr, p8, ld, scale, scale_const}; }
+// ... against caller-owned weight rows (the operator entries): w_dev is bf16, or e4m3 bytes when the activation is
+static GemmArgs gemm_operands(const ActOperand& a, const void* w_dev, int ldw, const float* wscale, const float* bias, int M, int N, int K, int tiles_n) {
+  GemmArgs g{};
+  g.A = a.p8 ? (const bf16*)a.p8 : a.p; g.lda = a.ld; g.W = (const bf16*)w_dev; g.ldw = ldw; g.bias = bias;
+  g.M = M; g.N = N; g.K = K; g.tiles_n = tiles_n;       // (tiles_n: column tiles of the 128 x 128 kernel; the 256 x 256 launch counts its own)
+  if (a.p8) { g.wscale = wscale; g.ascale = a.scale; g.ascale_const = a.scale_const; }
+  return g;
+}
+// ... against an engine matrix, in the activation's format: K is the matrix's padded row length in that format, N the columns the
+// launch stores.  (An e4m3 activation against a matrix ssp2_set_precision has not quantised leaves wscale null: the fp8 launch refuses it.)
+static GemmArgs bind(const Mat& m, const ActOperand& a, int M, int N) {
+  return a.p8 ? gemm_operands(a, m.w8, m.ld8, m.wscale, m.b, M, N, m.ld8, m.rows_pad / GEMM_BN)
+              : gemm_operands(a, m.w, m.ld, nullptr, m.b, M, N, m.ld, m.rows_pad / GEMM_BN);
+}
+static inline bool has_e4m3(const Mat& m) { return m.w8 != nullptr; }      // ssp2_set_precision has quantised it
+// ... against the N weight rows from row0 on (bf16): the evaluation tail's query and key / value slices of qkv
+static GemmArgs bind_rows(const Mat& m, int row0, const ActOperand& a, int M, int N) {
+  GemmArgs g = bind(m, a, M, N);
+  g.W += (size_t)row0 * m.ld; g.bias += row0; g.tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
+  return g;
+}
+// rows [row0, M) of an fc1 launch (the second launch of the prefix split): operand, per-row scales and output move on by row0 rows,
+// whose elements are bytes for the fp8 fc1 (e4m3 in, e4m3 out) and bf16 otherwise
+static GemmArgs gemm_rows_from(const GemmArgs& g, int row0) {
+  GemmArgs r = g;
+  const size_t esz = g.wscale ? 1 : sizeof(bf16);
+  r.M = g.M - row0; r.ascale = g.ascale ? g.ascale + row0 : nullptr;
+  r.A = (const bf16*)((const uint8_t*)g.A + (size_t)row0 * g.lda * esz); r.out = (bf16*)((uint8_t*)g.out + (size_t)row0 * g.ldo * esz);
+  return r;
+}
+
+// The one table from what a launch is at run time — epilogue, score site (g.score_site), operand format, and the width lnv = dim / 256
+// of a LayerNorm fused behind a residual epilogue (ln_fusable; 0 = none) — to the template instantiation that runs it.  bf16 operands go
+// through launch_gemm's choice of tile, e4m3 operands have the 256 x 256 kernel only.  The forms listed are the ones the library
+// launches: anything else is refused, not instantiated (tests/test_host_cpu.py counts the gemm256 forms of the product build).
+static_assert(SSP2_EPI_BF16 == EPI_BF16 && SSP2_EPI_RESID == EPI_RESID && SSP2_EPI_GELU == EPI_FC1, "the operator entries pass their epilogue code on as it is");
+static int dispatch_gemm(ssp2_engine* e, int epi, bool f8, const GemmArgs& g, int klass, int lnv = 0) {
+  const int site = g.score_site;
+#define GEMM_FORM(EPI_, SITE_) (f8 ? launch_gemm256<EPI_, SITE_, true>(e, g, klass) : launch_gemm<EPI_, SITE_>(e, g, klass))
+  if (epi == EPI_BF16 && !site && !lnv) return GEMM_FORM(EPI_BF16, 0);
+  if (epi == EPI_RESID && !site && lnv) return f8 ? launch_resid_ln<true>(e, g, lnv, klass) : launch_resid_ln<false>(e, g, lnv, klass);
+  if (epi == EPI_RESID && !site) return GEMM_FORM(EPI_RESID, 0);
+  if (epi == EPI_FC1 && !lnv && site == 1) return GEMM_FORM(EPI_FC1, 1);
+  if (epi == EPI_FC1 && !lnv && site == 2) return GEMM_FORM(EPI_FC1, 2);
+  if (epi == EPI_FC1 && !lnv && site == 0) return GEMM_FORM(EPI_FC1, 0);
+#undef GEMM_FORM
+  return fail(SSP2_EINVAL, "no GEMM kernel for epilogue %d with score site %d, %s operands, fused LayerNorm width %d", epi, site, f8 ? "e4m3" : "bf16", lnv);
+}
+
 static int launch_ln(ssp2_engine* e, const float* x, size_t in_stride, const float* g, const float* b, bf16* y,
                      int out_ld, int rows, int D, RowMap gather = RowMap{0, 0, 0}, uint8_t* y8 = nullptr, float* ascale = nullptr) {
   ProfScope ps(e, SSP2_K_LN, 0, (double)rows * D * (4.0 + (y8 ? 1.0 : 2.0)));     // fp32 row in, bf16 / e4m3 row out
@@ -462,11 +524,12 @@ static bool attn_streams(int mode, int dh, int tokens) {
   return attn_stream_ok(dh, tokens) && (mode >= 2 || (mode == 1 && !attn_resident(dh, tokens)));
 }
 // which geometries have a persistent kernel (the ones that can write the e4m3 output); never the streaming route
-static bool attn_persistent(const ssp2_engine* e) {
-  const int nt = (e->tokens + 31) / 32;
-  if (attn_streams(e->opt[SSP2_OPT_ATTN_STREAM], e->dh, e->tokens)) return false;
-  return e->opt[SSP2_OPT_ATTN_PERSIST] && ((e->dh == 64 && nt >= 4 && nt <= 7) || (e->dh == 80 && nt == 9 && e->tokens == 257));
+static bool attn_persistent_for(int stream, int persist, int dh, int tokens) {
+  const int nt = (tokens + 31) / 32;
+  if (attn_streams(stream, dh, tokens)) return false;
+  return persist && ((dh == 64 && nt >= 4 && nt <= 7) || (dh == 80 && nt == 9 && tokens == 257));
 }
+static bool attn_persistent(const ssp2_engine* e) { return attn_persistent_for(e->opt[SSP2_OPT_ATTN_STREAM], e->opt[SSP2_OPT_ATTN_PERSIST], e->dh, e->tokens); }
 // geometries launch_attn below has a kernel for under the streaming mode `stream` — checked when an engine is created, so that an
 // unsupported geometry fails THERE and not at the first forward
 static bool attn_supported(int dh, int tokens, int stream = 0) {
@@ -1082,9 +1145,7 @@ int ssp2_embed(ssp2_handle e, const float* pixels_dev, int n, float* x_dev, int 
                        e->d.patch, e->side, e->kpe, e->kpe_pad);
     HIPCHK(hipGetLastError());
   }
-  GemmArgs g{};
-  g.A = e->a_pe; g.lda = e->kpe_pad; g.W = e->patch.w; g.ldw = e->patch.ld; g.bias = e->patch.b;
-  g.M = n * e->patches; g.N = D; g.K = e->kpe_pad; g.tiles_n = e->patch.rows_pad / GEMM_BN;
+  GemmArgs g = bind(e->patch, act_bf16(e->a_pe, e->kpe_pad), n * e->patches, D);
   g.x = x_dev; g.ldx = D; g.pos = e->pos; g.patches = e->patches; g.prefix = e->prefix; g.group = rm.group; g.mpad = rm.mpad; g.n_img = n;
   return launch_gemm<EPI_PATCH>(e, g, SSP2_K_GEMM_PATCH);
 }
@@ -1099,6 +1160,144 @@ int ssp2_layers_from(ssp2_handle e, const float* x_in, float* x, int n, int l_be
   return ssp2_layers_prefix(e, x_in, x, n, l_begin, l_end, attn_skip, score_site, score_chain, score_group, n, batch_scores, score_ld);
 }
 
+// The block loop's LayerNorm output lives in hbuf (bf16) or, for a projection on e4m3 operands, in hbuf8 + hscale (e4m3 bytes, one scale
+// per row).  Three things must agree on that: the standalone LayerNorm that writes it, the LayerNorm fused behind a residual GEMM (lab
+// build) that writes it instead, and the operand the next projection binds.
+static int ln_to_hbuf(ssp2_engine* e, const float* x, const float* gm, const float* bt, int M, bool fp8, bool* h_ready) {
+  const int D = e->d.dim;
+  if (*h_ready) { *h_ready = false; return 0; }      // a residual GEMM has written it already: the hand-off is used up
+  return fp8 ? launch_ln(e, x, D, gm, bt, nullptr, e->ld8_dim, M, D, RowMap{0, 0, 0}, e->hbuf8, e->hscale) : launch_ln(e, x, D, gm, bt, e->hbuf, D, M, D);
+}
+static void fuse_ln_to_hbuf(const ssp2_engine* e, GemmArgs& a, const float* gm, const float* bt, bool fp8) {
+  a.ln_g = gm; a.ln_b = bt; a.ln_eps = e->d.ln_eps;
+  if (fp8) { a.ln_out8 = e->hbuf8; a.ln_ld = e->ld8_dim; a.ln_ascale = e->hscale; } else { a.ln_out = e->hbuf; a.ln_ld = e->d.dim; }
+}
+static ActOperand hbuf_operand(const ssp2_engine* e, bool fp8) { return fp8 ? act_e4m3(e->hbuf8, e->ld8_dim, e->hscale) : act_bf16(e->hbuf, e->d.dim); }
+
+// One ssp2_layers_prefix call: what its argument checks derive, and (last line) the two things that change from block to block
+struct LayersCall {
+  float* x; const uint8_t* attn_skip; int l_end;
+  int n, M; RowMap rm;                        // images and token-matrix rows of the launch
+  int score_site, score_chain; bool scores_only; float* batch_scores; int score_ld;
+  bool fused;                                 // the fc1 epilogue scores (a 128-row tile then spans at most two samples); else the standalone L2 kernel
+  bool split; int ns, M0;                     // hook on the leading ns images only: fc1 runs as rows [0, M0) scored + rows [M0, M) plain
+  int grp, n_groups; size_t group_stride;     // score groups of the hooked images
+  // fp8 mode: the three large projections of a launch with >= 4096 rows run on e4m3 operands (LayerNorm and the fc1
+  // epilogue write the activation as e4m3 bytes); attention, the out-projection and small launches stay bf16
+  bool f8, f8_fc1;
+  // xsrc: where the residual stream is READ — x_in for the block the call enters with (LayerNorm input and the first residual add),
+  // x from the first residual add on (out of place for one residual epilogue, no copy of the stream)
+  // h_ready: hbuf / hbuf8 already holds the LayerNorm the next projection reads (written by a residual GEMM)
+  const float* xsrc; bool h_ready;
+};
+static inline bool attn_skipped(const ssp2_engine* e, const LayersCall& c, int l) { return e->layers[l].attn_dropped || (c.attn_skip && c.attn_skip[l]); }
+
+// The attention half of block l: LN1, QKV, attention, out-projection + residual
+static int attn_half(ssp2_engine* e, LayersCall& c, int l) {
+  int rc;
+  Layer& L = e->layers[l];
+  const int D = e->d.dim, M = c.M;
+  if ((rc = ln_to_hbuf(e, c.xsrc, L.ln1_g, L.ln1_b, M, c.f8, &c.h_ready))) return rc;
+  GemmArgs q = bind(L.qkv, hbuf_operand(e, c.f8), M, 3 * D);
+  q.out = e->qkvbuf; q.ldo = 3 * D;
+  if ((rc = dispatch_gemm(e, EPI_BF16, c.f8, q, SSP2_K_GEMM_QKV))) return rc;
+  // fp8 out-projection (SSP2_OPT_FP8_PROJ): the persistent attention kernel writes e4m3(o * 16) bytes, the projection runs on
+  // e4m3 operands and divides the 16 out in its epilogue
+  // (during ssp2_fp8_calibrate_* the projection stays on bf16 and the block's max |o| is recorded)
+  const bool f8_proj = c.f8 && e->opt[SSP2_OPT_FP8_PROJ] && attn_persistent(e) && has_e4m3(L.proj) && D % 64 == 0 && !e->fp8_calibrating;
+  if ((rc = launch_attn(e, c.n, c.rm, false, f8_proj ? e->obuf8 : nullptr, L.o8_scale))) return rc;
+  if (c.f8 && e->fp8_calibrating && e->attn_amax) {
+    ProfScope ps(e, SSP2_K_OTHER);
+    hipLaunchKernelGGL(absmax_bf16_kernel, dim3(1024), dim3(256), 0, e->stream, e->obuf, (long)M, D, D, e->attn_amax + l);
+    HIPCHK(hipGetLastError());
+  }
+  GemmArgs p = bind(L.proj, f8_proj ? act_e4m3(e->obuf8, e->ld8_dim, nullptr, 1.0f / L.o8_scale) : act_bf16(e->obuf, D), M, D);
+  p.x = c.x; p.ldx = D; p.xin = c.xsrc;
+  const int lnv = ln_fusable(e, M, D, f8_proj);        // + LN2 of this layer: fc1's operand
+  if (lnv) fuse_ln_to_hbuf(e, p, L.ln2_g, L.ln2_b, c.f8_fc1);
+  if ((rc = dispatch_gemm(e, EPI_RESID, f8_proj, p, SSP2_K_GEMM_PROJ, lnv))) return rc;
+  c.h_ready = lnv != 0;
+  c.xsrc = c.x;
+  return 0;
+}
+
+// The stage-1 hook of block l: the hooked images' activation norms, summed per score group into the block's row of batch_scores
+static int score_finish(ssp2_engine* e, const LayersCall& c, int l) {
+  const Layer& L = e->layers[l];
+  float* row = c.batch_scores + (size_t)l * c.score_ld;
+  if (c.fused) {
+    ProfScope ps(e, SSP2_K_SCORE_FINISH);
+    hipLaunchKernelGGL(score_norms_from_slab_kernel, dim3((L.ld_int + 255) / 256, c.ns), dim3(256), 0, e->stream,
+                       e->slab, e->norms, c.ns, c.rm, L.ld_int, c.score_chain);
+    hipLaunchKernelGGL(score_colsum_kernel, dim3((L.ld_int + 255) / 256, c.n_groups), dim3(256), 0, e->stream, e->norms, row,
+                       c.group_stride, c.ns, c.grp, L.ld_int, c.score_chain);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  const bf16* seen = (c.score_site == SSP2_SCORE_PRE_GELU) ? e->prebuf : e->actbuf;
+  ProfScope ps(e, SSP2_K_ACT_L2);
+  return act_l2_impl(e->stream, seen, 0, c.ns, c.rm, L.d_int, L.ld_int, c.score_chain, c.grp, e->norms, row, c.group_stride);
+}
+
+// The MLP half of block l: LN2, fc1 + GELU (with the scoring epilogue where the call hooks it), the score finish, fc2 + residual
+static int mlp_half(ssp2_engine* e, LayersCall& c, int l) {
+  int rc = 0;
+  Layer& L = e->layers[l];
+  const int D = e->d.dim, M = c.M;
+  const bool f8 = c.f8_fc1;                      // fc1 and fc2 of a block share a format: the activation between them is e4m3 bytes or bf16
+  const int ld8_int = ceil_to(L.ld_int, 128);
+  if ((rc = ln_to_hbuf(e, c.xsrc, L.ln2_g, L.ln2_b, M, f8, &c.h_ready))) return rc;
+  GemmArgs f = bind(L.fc1, hbuf_operand(e, f8), M, f8 ? ld8_int : L.ld_int);
+  if (f8) { f.out = (bf16*)e->act8; f.ldo = ld8_int; }      // e4m3 bytes out; the pad columns up to 128 are written (zeros)
+  else { f.out = e->actbuf; f.ldo = L.ld_int; }
+  f.score_site = c.fused ? c.score_site : 0; f.tokens = e->tokens; f.slab = e->slab; f.slab_ld = L.ld_int;
+  f.group = c.rm.group; f.mpad = c.rm.mpad; f.n_img = c.ns;
+  f.group_m = 8;   // 8 x 8 tile patches per XCD: the 4.7 MB fc1 weight no longer thrashes the 4 MiB L2 (PMC: FETCH_SIZE / 3.7)
+  // unfused pre-GELU scoring (models with < 128 tokens): the hook sees fc1's output, fc2 consumes the GELU
+  // of it, so the epilogue also stores the pre-activation for the standalone L2 kernel to read.
+  f.out2 = (c.score_site == SSP2_SCORE_PRE_GELU && !c.fused) ? e->prebuf : nullptr;
+  if (c.split && c.fused) {
+    // the hooked slabs with the scoring epilogue, the rest of the launch (the search's candidates) without it
+    // (one operation as far as the zigzag goes: both launches walk in the direction the whole launch would have taken, the part
+    // that direction meets first goes first)
+    GemmArgs r = gemm_rows_from(f, c.M0);
+    r.score_site = 0; r.n_img = c.n - c.ns;
+    f.M = c.M0;
+    const int dir = next_dir(e);
+    e->zig_hold = dir;
+    if (!dir) rc = dispatch_gemm(e, EPI_FC1, f8, f, SSP2_K_GEMM_FC1);
+    if (!rc) rc = dispatch_gemm(e, EPI_FC1, f8, r, SSP2_K_GEMM_FC1);
+    if (!rc && dir) rc = dispatch_gemm(e, EPI_FC1, f8, f, SSP2_K_GEMM_FC1);
+    e->zig_hold = -1;                             // (on the error paths too)
+  } else {
+    rc = dispatch_gemm(e, EPI_FC1, f8, f, SSP2_K_GEMM_FC1);
+  }
+  if (rc) return rc;
+  if (f8 && e->fp8_calibrating && e->act8_top) {       // calibration pass: how much of the GELU output did the saturating e4m3 cast put on its top code?
+    ProfScope ps(e, SSP2_K_OTHER);
+    hipLaunchKernelGGL(e4m3_top_code_count_kernel, dim3(1024), dim3(256), 0, e->stream, e->act8, (long)M, ceil_to(L.d_int, 16), ld8_int, e->act8_top);
+    HIPCHK(hipGetLastError());
+  }
+  if (c.score_site && (rc = score_finish(e, c, l))) return rc;
+  if (c.scores_only && l + 1 == c.l_end) return 0;            // nothing reads x behind the last hooked activation
+  GemmArgs o = bind(L.fc2, f8 ? act_e4m3(e->act8, ld8_int, nullptr) : act_bf16(e->actbuf, L.ld_int), M, D);
+  o.x = c.x; o.ldx = D; o.xin = c.xsrc;
+  // + the LayerNorm the NEXT layer of this call starts with: LN1 of layer l + 1, or its LN2 when its attention is skipped
+  int lnv = 0;
+  if (l + 1 < c.l_end) {
+    const Layer& Ln = e->layers[l + 1];
+    const bool skip_n = attn_skipped(e, c, l + 1);
+    if (skip_n ? (Ln.ln_set[2] && Ln.ln_set[3]) : (Ln.ln_set[0] && Ln.ln_set[1])) {
+      lnv = ln_fusable(e, M, f8 ? ld8_int : L.ld_int, f8);
+      if (lnv) fuse_ln_to_hbuf(e, o, skip_n ? Ln.ln2_g : Ln.ln1_g, skip_n ? Ln.ln2_b : Ln.ln1_b, skip_n ? c.f8_fc1 : c.f8);
+    }
+  }
+  if ((rc = dispatch_gemm(e, EPI_RESID, f8, o, SSP2_K_GEMM_FC2, lnv))) return rc;
+  c.h_ready = lnv != 0;
+  c.xsrc = c.x;
+  return 0;
+}
+
 // score_images < n: only the LEADING score_images images of the launch are hooked (whole slabs of the slab layout).  This is the depth
 // search's baseline doubling as the stage-1 pass (reference: ONE loader and ONE batch_limit feed both stages,
 // adaptation-for-Pures-framework/mask_conjunction.py:276-281, :327): slot 0 of the layer-major launch is scored, the candidates' slots
@@ -1111,175 +1310,35 @@ int ssp2_layers_prefix(ssp2_handle e, const float* x_in, float* x, int n, int l_
   if (score_images <= 0 || score_images > n) return fail(SSP2_EINVAL, "score_images=%d outside (0, n=%d]", score_images, n);
   if (!x) return fail(SSP2_EINVAL, "null x");
   if (l_begin < 0 || l_end > e->d.depth || l_begin > l_end) return fail(SSP2_EINVAL, "bad layer range [%d,%d)", l_begin, l_end);
-  const bool scores_only = (score_site & SSP2_SCORE_ONLY) != 0;
+  LayersCall c{};
+  c.scores_only = (score_site & SSP2_SCORE_ONLY) != 0;
   score_site &= ~SSP2_SCORE_ONLY;
   if (score_site < 0 || score_site > 2) return fail(SSP2_EINVAL, "bad score_site %d", score_site);
-  if (scores_only && !score_site) return fail(SSP2_EINVAL, "SSP2_SCORE_ONLY without a score site");
+  if (c.scores_only && !score_site) return fail(SSP2_EINVAL, "SSP2_SCORE_ONLY without a score site");
   if (score_site && (!batch_scores || score_ld < e->ld_int_max)) return fail(SSP2_EINVAL, "batch_scores needs ld >= %d", e->ld_int_max);
-  const RowMap rm = make_rowmap(e->tokens, n, score_group);
-  const int D = e->d.dim, M = (int)total_rows(rm, n);
-  const bool prefix = score_site && score_images < n;
-  if (prefix && (rm.group <= 0 || score_images % rm.group != 0 || scores_only))
+  c.x = x; c.attn_skip = attn_skip; c.l_end = l_end;
+  c.n = n; c.rm = make_rowmap(e->tokens, n, score_group); c.M = (int)total_rows(c.rm, n);
+  c.score_site = score_site; c.score_chain = score_chain; c.batch_scores = batch_scores; c.score_ld = score_ld;
+  c.split = score_site && score_images < n;
+  if (c.split && (c.rm.group <= 0 || score_images % c.rm.group != 0 || c.scores_only))
     return fail(SSP2_EINVAL, "score_images=%d < n=%d needs the slab layout, whole slabs (group %d) and no SSP2_SCORE_ONLY", score_images, n, score_group);
-  const int ns = score_site ? score_images : n;                                   // images that are hooked
-  const int M0 = prefix ? (score_images / rm.group) * rm.mpad : M;                 // rows of the scored prefix: whole padded slabs
-  const int grp = (score_group <= 0 || score_group > n) ? n : score_group;
-  const int n_groups = (ns + grp - 1) / grp;
-  const size_t group_stride = (size_t)e->d.depth * score_ld;
-  const bool fused = score_site && e->tokens >= GEMM_BM;   // a 128-row tile then spans at most two samples
-  // fp8 mode: the three large projections of a launch with >= 4096 rows run on e4m3 operands (LayerNorm and the fc1
-  // epilogue write the activation as e4m3 bytes); attention, the out-projection and small launches stay bf16
-  const bool f8 = e->fp8 && M >= big_tile_min_rows(e);
-  const bool f8_fc1 = f8 && fused_ok_for_fp8(score_site, e->tokens);
-  bool h_ready = false;          // hbuf / hbuf8 already holds the LayerNorm the next projection reads (written by a residual GEMM)
-  // x_in: the residual stream ENTERING block l_begin is read from there (LayerNorm input and the first residual add), everything
-  // from the first residual add on lives in x — out of place for one residual epilogue, no copy of the stream
-  const float* xsrc = (x_in && x_in != x) ? x_in : x;
-  auto set_ln = [&](GemmArgs& a, const float* gm, const float* bt, bool to_fp8) {
-    a.ln_g = gm; a.ln_b = bt; a.ln_eps = e->d.ln_eps;
-    if (to_fp8) { a.ln_out8 = e->hbuf8; a.ln_ld = e->ld8_dim; a.ln_ascale = e->hscale; } else { a.ln_out = e->hbuf; a.ln_ld = D; }
-  };
+  c.ns = score_site ? score_images : n;                                            // images that are hooked
+  c.M0 = c.split ? (score_images / c.rm.group) * c.rm.mpad : c.M;                  // rows of the scored prefix: whole padded slabs
+  c.grp = (score_group <= 0 || score_group > n) ? n : score_group;
+  c.n_groups = (c.ns + c.grp - 1) / c.grp;
+  c.group_stride = (size_t)e->d.depth * score_ld;
+  c.fused = score_site && e->tokens >= GEMM_BM;
+  c.f8 = e->fp8 && c.M >= big_tile_min_rows(e);
+  c.f8_fc1 = c.f8 && fused_ok_for_fp8(score_site, e->tokens);
+  c.xsrc = (x_in && x_in != x) ? x_in : x;
   for (int l = l_begin; l < l_end; ++l) {
-    Layer& L = e->layers[l];
-    const bool skip = L.attn_dropped || (attn_skip && attn_skip[l]);
-    if (!(L.ln_set[2] && L.ln_set[3] && L.fc1.w_set && L.fc1.b_set && L.fc2.w_set && L.fc2.b_set))
-      return fail(SSP2_ESTATE, "layer %d MLP weights not loaded", l);
-    if (!skip) {
-      if (!(L.ln_set[0] && L.ln_set[1] && L.qkv.w_set && L.qkv.b_set && L.proj.w_set && L.proj.b_set))
-        return fail(SSP2_ESTATE, "layer %d attention weights not loaded", l);
-      GemmArgs q{};
-      q.bias = L.qkv.b; q.M = M; q.N = 3 * D; q.tiles_n = L.qkv.rows_pad / GEMM_BN; q.out = e->qkvbuf; q.ldo = 3 * D;
-      if (f8) {
-        if (!h_ready && (rc = launch_ln(e, xsrc, D, L.ln1_g, L.ln1_b, nullptr, e->ld8_dim, M, D, RowMap{0, 0, 0}, e->hbuf8, e->hscale))) return rc;
-        q.A = (const bf16*)e->hbuf8; q.lda = e->ld8_dim; q.W = (const bf16*)L.qkv.w8; q.ldw = L.qkv.ld8; q.K = e->ld8_dim; q.wscale = L.qkv.wscale; q.ascale = e->hscale;
-        if ((rc = launch_gemm256<EPI_BF16, 0, true>(e, q, SSP2_K_GEMM_QKV))) return rc;
-      } else {
-        if (!h_ready && (rc = launch_ln(e, xsrc, D, L.ln1_g, L.ln1_b, e->hbuf, D, M, D))) return rc;
-        q.A = e->hbuf; q.lda = D; q.W = L.qkv.w; q.ldw = L.qkv.ld; q.K = D;
-        if ((rc = launch_gemm<EPI_BF16>(e, q, SSP2_K_GEMM_QKV))) return rc;
-      }
-      h_ready = false;
-      // fp8 out-projection (SSP2_OPT_FP8_PROJ): the persistent attention kernel writes e4m3(o * 16) bytes, the projection runs on
-      // e4m3 operands and divides the 16 out in its epilogue
-      // (during ssp2_fp8_calibrate_* the projection stays on bf16 and the block's max |o| is recorded)
-      const bool f8_proj = f8 && e->opt[SSP2_OPT_FP8_PROJ] && attn_persistent(e) && L.proj.w8 && D % 64 == 0 && !e->fp8_calibrating;
-      if ((rc = launch_attn(e, n, rm, false, f8_proj ? e->obuf8 : nullptr, L.o8_scale))) return rc;
-      if (f8 && e->fp8_calibrating && e->attn_amax) {
-        ProfScope ps(e, SSP2_K_OTHER);
-        hipLaunchKernelGGL(absmax_bf16_kernel, dim3(1024), dim3(256), 0, e->stream, e->obuf, (long)M, D, D, e->attn_amax + l);
-        HIPCHK(hipGetLastError());
-      }
-      GemmArgs p{};
-      p.bias = L.proj.b;
-      p.M = M; p.N = D; p.tiles_n = L.proj.rows_pad / GEMM_BN; p.x = x; p.ldx = D; p.xin = xsrc;
-      if (f8_proj) {
-        p.A = (const bf16*)e->obuf8; p.lda = e->ld8_dim; p.W = (const bf16*)L.proj.w8; p.ldw = L.proj.ld8; p.K = e->ld8_dim; p.wscale = L.proj.wscale;
-        p.ascale_const = 1.0f / L.o8_scale;
-      } else {
-        p.A = e->obuf; p.lda = D; p.W = L.proj.w; p.ldw = L.proj.ld; p.K = D;
-      }
-      if (const int lnv = ln_fusable(e, M, D, f8_proj)) {        // + LN2 of this layer: fc1's operand
-        set_ln(p, L.ln2_g, L.ln2_b, f8_fc1);
-        if ((rc = f8_proj ? launch_resid_ln<true>(e, p, lnv, SSP2_K_GEMM_PROJ) : launch_resid_ln<false>(e, p, lnv, SSP2_K_GEMM_PROJ))) return rc;
-        h_ready = true;
-      } else if ((rc = f8_proj ? launch_gemm256<EPI_RESID, 0, true>(e, p, SSP2_K_GEMM_PROJ) : launch_gemm<EPI_RESID>(e, p, SSP2_K_GEMM_PROJ))) return rc;
-      xsrc = x;
+    const Layer& L = e->layers[l];
+    if (!mlp_loaded(L)) return fail(SSP2_ESTATE, "layer %d MLP weights not loaded", l);
+    if (!attn_skipped(e, c, l)) {
+      if (!attn_loaded(L)) return fail(SSP2_ESTATE, "layer %d attention weights not loaded", l);
+      if ((rc = attn_half(e, c, l))) return rc;
     }
-    const int ld8_int = ceil_to(L.ld_int, 128);
-    GemmArgs f{};
-    f.bias = L.fc1.b; f.M = M; f.tiles_n = L.fc1.rows_pad / GEMM_BN;
-    if (f8_fc1) {
-      if (!h_ready && (rc = launch_ln(e, xsrc, D, L.ln2_g, L.ln2_b, nullptr, e->ld8_dim, M, D, RowMap{0, 0, 0}, e->hbuf8, e->hscale))) return rc;
-      f.A = (const bf16*)e->hbuf8; f.lda = e->ld8_dim; f.W = (const bf16*)L.fc1.w8; f.ldw = L.fc1.ld8; f.K = e->ld8_dim; f.wscale = L.fc1.wscale; f.ascale = e->hscale;
-      f.N = ld8_int; f.out = (bf16*)e->act8; f.ldo = ld8_int;      // e4m3 bytes out; the pad columns up to 128 are written (zeros)
-    } else {
-      if (!h_ready && (rc = launch_ln(e, xsrc, D, L.ln2_g, L.ln2_b, e->hbuf, D, M, D))) return rc;
-      f.A = e->hbuf; f.lda = D; f.W = L.fc1.w; f.ldw = L.fc1.ld; f.K = D;
-      f.N = L.ld_int; f.out = e->actbuf; f.ldo = L.ld_int;
-    }
-    h_ready = false;
-    const bool f8_mlp = f.wscale != nullptr;
-    f.score_site = fused ? score_site : 0; f.tokens = e->tokens; f.slab = e->slab; f.slab_ld = L.ld_int;
-    f.group = rm.group; f.mpad = rm.mpad; f.n_img = ns;
-    f.group_m = 8;   // 8 x 8 tile patches per XCD: the 4.7 MB fc1 weight no longer thrashes the 4 MiB L2 (PMC: FETCH_SIZE / 3.7)
-    // unfused pre-GELU scoring (models with < 128 tokens): the hook sees fc1's output, fc2 consumes the GELU
-    // of it, so the epilogue also stores the pre-activation for the standalone L2 kernel to read.
-    f.out2 = (score_site == SSP2_SCORE_PRE_GELU && !fused) ? e->prebuf : nullptr;
-    auto run_fc1 = [&](GemmArgs& a) -> int {
-      if (f8_mlp) {
-        if (a.score_site == 1) return launch_gemm256<EPI_FC1, 1, true>(e, a, SSP2_K_GEMM_FC1);
-        if (a.score_site == 2) return launch_gemm256<EPI_FC1, 2, true>(e, a, SSP2_K_GEMM_FC1);
-        return launch_gemm256<EPI_FC1, 0, true>(e, a, SSP2_K_GEMM_FC1);
-      }
-      if (a.score_site == 1) return launch_gemm<EPI_FC1, 1>(e, a, SSP2_K_GEMM_FC1);
-      if (a.score_site == 2) return launch_gemm<EPI_FC1, 2>(e, a, SSP2_K_GEMM_FC1);
-      return launch_gemm<EPI_FC1, 0>(e, a, SSP2_K_GEMM_FC1);
-    };
-    if (prefix && fused) {
-      // the hooked slabs with the scoring epilogue, the rest of the launch (the search's candidates) without it
-      // (one operation as far as the zigzag goes: both launches walk in the direction the whole launch would have taken, the part
-      // that direction meets first goes first)
-      GemmArgs r = f;
-      f.M = M0;
-      const int dir = next_dir(e);
-      e->zig_hold = dir;
-      if (!dir && (rc = run_fc1(f))) { e->zig_hold = -1; return rc; }
-      r.M = M - M0; r.score_site = 0; r.n_img = n - ns;
-      if (f8_mlp) {
-        r.A = (const bf16*)((const uint8_t*)r.A + (size_t)M0 * r.lda); r.ascale = r.ascale ? r.ascale + M0 : nullptr;
-        r.out = (bf16*)((uint8_t*)r.out + (size_t)M0 * r.ldo);
-      } else {
-        r.A = r.A + (size_t)M0 * r.lda; r.out = r.out + (size_t)M0 * r.ldo;
-      }
-      rc = run_fc1(r);
-      if (!rc && dir) rc = run_fc1(f);
-      e->zig_hold = -1;
-    } else {
-      rc = run_fc1(f);
-    }
-    if (rc) return rc;
-    if (f8_mlp && e->fp8_calibrating && e->act8_top) {       // calibration pass: how much of the GELU output did the saturating e4m3 cast put on its top code?
-      ProfScope ps(e, SSP2_K_OTHER);
-      hipLaunchKernelGGL(e4m3_top_code_count_kernel, dim3(1024), dim3(256), 0, e->stream, e->act8, (long)M, ceil_to(L.d_int, 16), ld8_int, e->act8_top);
-      HIPCHK(hipGetLastError());
-    }
-    if (score_site) {
-      float* row = batch_scores + (size_t)l * score_ld;
-      if (fused) {
-        ProfScope ps(e, SSP2_K_SCORE_FINISH);
-        hipLaunchKernelGGL(score_norms_from_slab_kernel, dim3((L.ld_int + 255) / 256, ns), dim3(256), 0, e->stream,
-                           e->slab, e->norms, ns, rm, L.ld_int, score_chain);
-        hipLaunchKernelGGL(score_colsum_kernel, dim3((L.ld_int + 255) / 256, n_groups), dim3(256), 0, e->stream, e->norms, row,
-                           group_stride, ns, grp, L.ld_int, score_chain);
-        HIPCHK(hipGetLastError());
-      } else {
-        const bf16* seen = (score_site == SSP2_SCORE_PRE_GELU) ? e->prebuf : e->actbuf;
-        ProfScope ps(e, SSP2_K_ACT_L2);
-        if ((rc = act_l2_impl(e->stream, seen, 0, ns, rm, L.d_int, L.ld_int, score_chain, grp, e->norms, row, group_stride))) return rc;
-      }
-    }
-    if (scores_only && l + 1 == l_end) break;            // nothing reads x behind the last hooked activation
-    GemmArgs o{};
-    o.bias = L.fc2.b; o.M = M; o.N = D; o.tiles_n = L.fc2.rows_pad / GEMM_BN; o.x = x; o.ldx = D; o.xin = xsrc;
-    // + the LayerNorm the NEXT layer of this call starts with: LN1 of layer l + 1, or its LN2 when its attention is skipped
-    int lnv = 0;
-    if (l + 1 < l_end) {
-      Layer& Ln = e->layers[l + 1];
-      const bool skip_n = Ln.attn_dropped || (attn_skip && attn_skip[l + 1]);
-      if (skip_n ? (Ln.ln_set[2] && Ln.ln_set[3]) : (Ln.ln_set[0] && Ln.ln_set[1])) {
-        lnv = ln_fusable(e, M, f8_mlp ? ld8_int : L.ld_int, f8_mlp);
-        if (lnv) set_ln(o, skip_n ? Ln.ln2_g : Ln.ln1_g, skip_n ? Ln.ln2_b : Ln.ln1_b, skip_n ? f8_fc1 : f8);
-      }
-    }
-    if (f8_mlp) {
-      o.A = (const bf16*)e->act8; o.lda = ld8_int; o.W = (const bf16*)L.fc2.w8; o.ldw = L.fc2.ld8; o.K = ld8_int; o.wscale = L.fc2.wscale;
-      if ((rc = lnv ? launch_resid_ln<true>(e, o, lnv, SSP2_K_GEMM_FC2) : launch_gemm256<EPI_RESID, 0, true>(e, o, SSP2_K_GEMM_FC2))) return rc;
-    } else {
-      o.A = e->actbuf; o.lda = L.ld_int; o.W = L.fc2.w; o.ldw = L.fc2.ld; o.K = L.ld_int;
-      if ((rc = lnv ? launch_resid_ln<false>(e, o, lnv, SSP2_K_GEMM_FC2) : launch_gemm<EPI_RESID>(e, o, SSP2_K_GEMM_FC2))) return rc;
-    }
-    h_ready = lnv != 0;
-    xsrc = x;
+    if ((rc = mlp_half(e, c, l))) return rc;
   }
   return 0;
 }
@@ -1300,16 +1359,14 @@ static int head_impl(ssp2_engine* e, const float* x, size_t in_stride, int n, fl
       if ((rc = launch_ln(e, x + (size_t)t * D, in_stride, e->lnf_g, e->lnf_b, e->cls_h + (size_t)t * n * D, D, n, D, gather))) return rc;
   }
   float* lg = e->dist_head ? e->logits : (logits_dev ? logits_dev : e->logits);
-  GemmArgs g{};
-  g.A = e->cls_h; g.lda = D; g.W = e->head.w; g.ldw = e->head.ld; g.bias = e->head.b;
-  g.M = n; g.N = C; g.K = D; g.tiles_n = e->head.rows_pad / GEMM_BN; g.x = lg; g.ldx = C;
+  GemmArgs g = bind(e->head, act_bf16(e->cls_h, D), n, C);
+  g.x = lg; g.ldx = C;
   if ((rc = launch_gemm<EPI_F32>(e, g, SSP2_K_GEMM_HEAD))) return rc;
   if (e->dist_head) {   // head_dist on the DIST rows, then logits = 0.5f * bf16(a + b) (autocast's rounding points) and the top-1 of the mean in one kernel
     float* lb = e->logits + (size_t)n * C;
     float* out = logits_dev ? logits_dev : e->logits + (size_t)2 * n * C;
-    GemmArgs h{};
-    h.A = e->cls_h + (size_t)n * D; h.lda = D; h.W = e->head_dist.w; h.ldw = e->head_dist.ld; h.bias = e->head_dist.b;
-    h.M = n; h.N = C; h.K = D; h.tiles_n = e->head_dist.rows_pad / GEMM_BN; h.x = lb; h.ldx = C;
+    GemmArgs h = bind(e->head_dist, act_bf16(e->cls_h + (size_t)n * D, D), n, C);
+    h.x = lb; h.ldx = C;
     if ((rc = launch_gemm<EPI_F32>(e, h, SSP2_K_GEMM_HEAD))) return rc;
     ProfScope ps(e, SSP2_K_OTHER);
     hipLaunchKernelGGL(dist_head_top1_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, lg, lb, out, n, C, pred, labels,
@@ -1365,7 +1422,7 @@ int ssp2_tail_group(ssp2_handle e, const float* x, int n_slot, int slots, int gr
   const int D = e->d.dim, M = (int)total_rows(rm, n), l = e->d.depth - 1;
   const int P = e->tail_rows, PN = P * n;              // rows the tail carries: CLS, and DIST with the distillation head
   Layer& L = e->layers[l];
-  if (!(L.ln_set[2] && L.ln_set[3] && L.fc1.w_set && L.fc1.b_set && L.fc2.w_set && L.fc2.b_set)) return fail(SSP2_ESTATE, "last layer MLP weights not loaded");
+  if (!mlp_loaded(L)) return fail(SSP2_ESTATE, "last layer MLP weights not loaded");
   // x_cls <- prefix rows 0..P-1 of x, prefix-major [P][n][D] (x itself is left untouched)
   if (rm.group > 0) {
     ProfScope ps(e, SSP2_K_OTHER);
@@ -1377,33 +1434,28 @@ int ssp2_tail_group(ssp2_handle e, const float* x, int n_slot, int slots, int gr
                               hipMemcpyDeviceToDevice, e->stream));
   }
   if (!attn_skip_last && !L.attn_dropped) {
-    if (!(L.ln_set[0] && L.ln_set[1] && L.qkv.w_set && L.qkv.b_set && L.proj.w_set && L.proj.b_set)) return fail(SSP2_ESTATE, "last layer attention weights not loaded");
+    if (!attn_loaded(L)) return fail(SSP2_ESTATE, "last layer attention weights not loaded");
     // keys / values need every token; the query, the out-projection and the MLP only the P prefix rows
     if ((rc = launch_ln(e, x, D, L.ln1_g, L.ln1_b, e->hbuf, D, M, D))) return rc;
-    GemmArgs kv{};
-    kv.A = e->hbuf; kv.lda = D; kv.W = L.qkv.w + (size_t)D * L.qkv.ld; kv.ldw = L.qkv.ld; kv.bias = L.qkv.b + D;
-    kv.M = M; kv.N = 2 * D; kv.K = D; kv.tiles_n = (2 * D + GEMM_BN - 1) / GEMM_BN; kv.out = e->qkvbuf + D; kv.ldo = 3 * D;
-    if ((rc = launch_gemm<EPI_BF16>(e, kv, SSP2_K_GEMM_QKV))) return rc;
+    GemmArgs kv = bind_rows(L.qkv, D, act_bf16(e->hbuf, D), M, 2 * D);            // weight rows [D, 3 D): keys and values
+    kv.out = e->qkvbuf + D; kv.ldo = 3 * D;
+    if ((rc = dispatch_gemm(e, EPI_BF16, false, kv, SSP2_K_GEMM_QKV))) return rc;
     if ((rc = launch_ln(e, e->x_cls, D, L.ln1_g, L.ln1_b, e->h_cls, D, PN, D))) return rc;     // the same rows' bits as the full LN1
-    GemmArgs q{};
-    q.A = e->h_cls; q.lda = D; q.W = L.qkv.w; q.ldw = L.qkv.ld; q.bias = L.qkv.b;
-    q.M = PN; q.N = D; q.K = D; q.tiles_n = (D + GEMM_BN - 1) / GEMM_BN; q.out = e->q_cls; q.ldo = D;
-    if ((rc = launch_gemm<EPI_BF16>(e, q, SSP2_K_GEMM_QKV))) return rc;
+    GemmArgs q = bind_rows(L.qkv, 0, act_bf16(e->h_cls, D), PN, D);               // weight rows [0, D): the queries
+    q.out = e->q_cls; q.ldo = D;
+    if ((rc = dispatch_gemm(e, EPI_BF16, false, q, SSP2_K_GEMM_QKV))) return rc;
     if ((rc = launch_attn(e, n, rm, true))) return rc;
-    GemmArgs p{};
-    p.A = e->o_cls; p.lda = D; p.W = L.proj.w; p.ldw = L.proj.ld; p.bias = L.proj.b;
-    p.M = PN; p.N = D; p.K = D; p.tiles_n = L.proj.rows_pad / GEMM_BN; p.x = e->x_cls; p.ldx = D;
-    if ((rc = launch_gemm<EPI_RESID>(e, p, SSP2_K_GEMM_PROJ))) return rc;
+    GemmArgs p = bind(L.proj, act_bf16(e->o_cls, D), PN, D);
+    p.x = e->x_cls; p.ldx = D;
+    if ((rc = dispatch_gemm(e, EPI_RESID, false, p, SSP2_K_GEMM_PROJ))) return rc;
   }
   if ((rc = launch_ln(e, e->x_cls, D, L.ln2_g, L.ln2_b, e->h_cls, D, PN, D))) return rc;
-  GemmArgs f{};
-  f.A = e->h_cls; f.lda = D; f.W = L.fc1.w; f.ldw = L.fc1.ld; f.bias = L.fc1.b;
-  f.M = PN; f.N = L.ld_int; f.K = D; f.tiles_n = L.fc1.rows_pad / GEMM_BN; f.out = e->act_cls; f.ldo = L.ld_int;
-  if ((rc = launch_gemm<EPI_FC1, 0>(e, f, SSP2_K_GEMM_FC1))) return rc;
-  GemmArgs o{};
-  o.A = e->act_cls; o.lda = L.ld_int; o.W = L.fc2.w; o.ldw = L.fc2.ld; o.bias = L.fc2.b;
-  o.M = PN; o.N = D; o.K = L.ld_int; o.tiles_n = L.fc2.rows_pad / GEMM_BN; o.x = e->x_cls; o.ldx = D;
-  if ((rc = launch_gemm<EPI_RESID>(e, o, SSP2_K_GEMM_FC2))) return rc;
+  GemmArgs f = bind(L.fc1, act_bf16(e->h_cls, D), PN, L.ld_int);
+  f.out = e->act_cls; f.ldo = L.ld_int;
+  if ((rc = dispatch_gemm(e, EPI_FC1, false, f, SSP2_K_GEMM_FC1))) return rc;
+  GemmArgs o = bind(L.fc2, act_bf16(e->act_cls, L.ld_int), PN, D);
+  o.x = e->x_cls; o.ldx = D;
+  if ((rc = dispatch_gemm(e, EPI_RESID, false, o, SSP2_K_GEMM_FC2))) return rc;
   return head_impl(e, e->x_cls, (size_t)D, n, logits_dev, pred, labels, correct, RowMap{0, 0, 0}, period, true);
 }
 
@@ -1567,14 +1619,45 @@ int ssp2_act_l2_accum(void* stream, const void* act, int dtype, int n, int token
   return act_l2_impl(stream, act, dtype, n, RowMap{tokens, 0, 0}, d, ld, chain, group, norms_ws, out, out_stride);
 }
 
-// CUs of the current device, for the persistent kernels' grids of the operator entries below (asked once)
-static int op_cu_count() {
+// The engine of an operator entry (ssp2_linear_*, ssp2_attention_*, ssp2_layernorm): a stack object that owns nothing, on the caller's
+// stream and the current device, with the FORWARD'S DEFAULTS for the options a GEMM or LayerNorm launch reads — so that an entry is the
+// forward's launch and not a copy of it.  rev >= 0: zigzag on, and next_dir() hands the entry's launch that direction (the forward
+// alternates it); rev < 0: the forward walk.  Asks the device for its CU count (once): the entries call it after their argument checks.
+static ssp2_engine op_engine(void* hip_stream, int rev = -1) {
   static int n_cu = 0;
   if (!n_cu) {
     int dev = 0; hipDeviceProp_t pr;
     n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
   }
-  return n_cu;
+  ssp2_engine e;
+  e.stream = (hipStream_t)hip_stream; e.n_cu = n_cu; e.dev = cur_device();
+  e.opt[SSP2_OPT_BIG_TILES] = e.opt[SSP2_OPT_FC1_BIG_TILES] = 1;
+  e.opt[SSP2_OPT_BIG_TILE_MIN_ROWS] = kBigTileMinRowsDefault;
+  { const char* v = getenv("SSP2_NT_STORES"); e.opt[SSP2_OPT_NT_STORES] = (v && *v) ? atoi(v) : 1; }      // the forward's default store policy
+  if (rev >= 0) { e.opt[SSP2_OPT_ZIGZAG] = 1; e.zig = rev; }
+  return e;
+}
+// ... of an attention entry: the geometry, and the forward's attention buffers pointed at the caller's
+static ssp2_engine op_attn_engine(void* hip_stream, int rev, int tokens, int heads, int d_h, const uint16_t* qkv_dev, const uint16_t* q_dev, uint16_t* out_dev, int ldo) {
+  ssp2_engine e = op_engine(hip_stream, rev);
+  e.d.dim = heads * d_h; e.d.heads = heads; e.tokens = tokens; e.dh = d_h;
+  e.qkvbuf = (bf16*)qkv_dev; e.q_cls = (bf16*)q_dev;
+  e.obuf = e.o_cls = (bf16*)out_dev; e.o_ld = ldo;
+  return e;
+}
+// what the three attention entries check alike: the counts, dim = heads * d_h, the bf16 output's row stride, the item count
+static int check_attn_args(const char* who, int n, int tokens, int heads, int d_h, int group, const uint16_t* out_dev, int ldo) {
+  if (n <= 0 || heads <= 0 || tokens <= 0 || group < 0) return fail(SSP2_EINVAL, "%s: n=%d heads=%d tokens=%d group=%d", who, n, heads, tokens, group);
+  if ((long)heads * d_h > (1 << 20) || (heads * d_h) % 8) return fail(SSP2_EINVAL, "%s: dim = heads * d_h = %ld (a multiple of 8)", who, (long)heads * d_h);
+  if (out_dev && (ldo < heads * d_h || ldo % 8)) return fail(SSP2_EINVAL, "%s: ldo=%d (>= dim %d, a multiple of 8)", who, ldo, heads * d_h);
+  if ((long)n * heads > 0x7fffffffL) return fail(SSP2_EINVAL, "%s: too many attention items", who);
+  return 0;
+}
+// what the two projection entries check of the epilogue's output: out / ldo (a multiple of ldo_mult) or x / ldx
+static int check_linear_out(const char* who, int epilogue, const void* out_dev, int ldo, int ldo_mult, const float* x_dev, int ldx, int N) {
+  if (epilogue == SSP2_EPI_BF16 || epilogue == SSP2_EPI_GELU) return (!out_dev || ldo < N || ldo % ldo_mult) ? fail(SSP2_EINVAL, "%s: out / ldo (>= N, a multiple of %d)", who, ldo_mult) : 0;
+  if (epilogue == SSP2_EPI_RESID) return (!x_dev || ldx < N || ldx % 4) ? fail(SSP2_EINVAL, "%s: x / ldx", who) : 0;
+  return fail(SSP2_EINVAL, "unknown epilogue %d", epilogue);
 }
 
 // The projection operator on its own (a3's building block): out = epilogue(A x W^T + bias) on caller-owned device
@@ -1586,39 +1669,24 @@ int ssp2_linear_bf16(void* hip_stream, int epilogue, const uint16_t* a_dev, int 
   if (M <= 0 || N <= 0 || K <= 0 || (K % GEMM_BK) || (N % 64)) return fail(SSP2_EINVAL, "linear: M=%d N=%d K=%d (K multiple of %d, N multiple of 64)", M, N, K, GEMM_BK);
   if (lda < K || ldw < K || (lda % 8) || (ldw % 8)) return fail(SSP2_EINVAL, "linear: lda=%d ldw=%d must be >= K and multiples of 8", lda, ldw);
   if (kernel < 0 || kernel > 2) return fail(SSP2_EINVAL, "kernel selector %d", kernel);
-  ssp2_engine e;
-  e.stream = (hipStream_t)hip_stream; e.n_cu = op_cu_count(); e.dev = cur_device();
-  e.opt[SSP2_OPT_BIG_TILES] = e.opt[SSP2_OPT_FC1_BIG_TILES] = 1;
-  e.opt[SSP2_OPT_BIG_TILE_MIN_ROWS] = kBigTileMinRowsDefault;
-  { const char* v = getenv("SSP2_NT_STORES"); e.opt[SSP2_OPT_NT_STORES] = (v && *v) ? atoi(v) : 1; }      // the forward's default store policy
-  GemmArgs g{};
-  g.A = (const bf16*)a_dev; g.lda = lda; g.W = (const bf16*)w_dev; g.ldw = ldw; g.bias = bias_dev;
-  g.M = M; g.N = N; g.K = K; g.tiles_n = ceil_to(N, 256) / GEMM_BN;
+  if (int rc = check_linear_out("linear", epilogue, out_dev, ldo, 8, x_dev, ldx, N)) return rc;
+  ssp2_engine e = op_engine(hip_stream);
+  // the kernel selector, said in the options the forward's routing (launch_gemm) reads: 1 = no big tiles, 2 = big tiles from the first row on
+  if (kernel == 1) e.opt[SSP2_OPT_BIG_TILES] = 0;
+  if (kernel == 2) e.opt[SSP2_OPT_BIG_TILE_MIN_ROWS] = 1;
+  GemmArgs g = gemm_operands(act_bf16((const bf16*)a_dev, lda), w_dev, ldw, nullptr, bias_dev, M, N, K, ceil_to(N, 256) / GEMM_BN);
   g.out = (bf16*)out_dev; g.ldo = ldo; g.x = x_dev; g.ldx = ldx;
-  const bool big = kernel == 2 || (kernel == 0 && M >= kBigTileMinRowsDefault);
-  switch (epilogue) {
-    case SSP2_EPI_BF16:
-      if (!out_dev || ldo < N || (ldo % 8)) return fail(SSP2_EINVAL, "linear: out / ldo");
-      return big ? launch_gemm256<EPI_BF16>(&e, g, -2) : launch_gemm_small<EPI_BF16>(&e, g, -2);
-    case SSP2_EPI_GELU:
-      if (!out_dev || ldo < N || (ldo % 8)) return fail(SSP2_EINVAL, "linear: out / ldo");
-      return big ? launch_gemm256<EPI_FC1, 0>(&e, g, -2) : launch_gemm_small<EPI_FC1, 0>(&e, g, -2);
-    case SSP2_EPI_RESID:
-      if (!x_dev || ldx < N || (ldx % 4)) return fail(SSP2_EINVAL, "linear: x / ldx");
 #ifdef SSP2_LAB
-      if (big && N % 256 == 0 && K / 64 >= 4) {     // SSP2_DEFER_RESID=1: the deferred residual, as the forward would take it
-        const char* v = getenv("SSP2_DEFER_RESID");
-        if (v && atoi(v)) {
-          static unsigned int* park[kMaxDevices] = {};
-          if (!park[e.dev] && hipMalloc((void**)&park[e.dev], (size_t)e.n_cu * 131072) != hipSuccess) return fail(SSP2_ENOMEM, "linear: parking area");
-          e.dg_scratch = park[e.dev];
-          return launch_gemm256<EPI_RESID, 1>(&e, g, -2);
-        }
-      }
-#endif
-      return big ? launch_gemm256<EPI_RESID>(&e, g, -2) : launch_gemm_small<EPI_RESID>(&e, g, -2);
-    default: return fail(SSP2_EINVAL, "unknown epilogue %d", epilogue);
+  if (epilogue == SSP2_EPI_RESID && e.opt[SSP2_OPT_BIG_TILES] && M >= big_tile_min_rows(&e) && N % 256 == 0 && K / 64 >= 4) {
+    const char* v = getenv("SSP2_DEFER_RESID");     // SSP2_DEFER_RESID=1: the deferred residual, as the forward would take it
+    if (v && atoi(v)) {
+      static unsigned int* park[kMaxDevices] = {};
+      if (!park[e.dev] && hipMalloc((void**)&park[e.dev], (size_t)e.n_cu * 131072) != hipSuccess) return fail(SSP2_ENOMEM, "linear: parking area");
+      e.dg_scratch = park[e.dev]; e.opt[SSP2_OPT_DEFER_RESID] = 1;
+    }
   }
+#endif
+  return dispatch_gemm(&e, epilogue, false, g, -2);
 }
 
 // The fp8 projection operator on its own: the forward's launch_gemm256<EPI, SCORE, true> (QKV, fc1 with its score sites, the
@@ -1642,30 +1710,15 @@ int ssp2_linear_e4m3(void* hip_stream, int epilogue, const uint8_t* a_dev, int l
     if (total_rows(make_rowmap(tokens, n_img, group), n_img) > M)
       return fail(SSP2_EINVAL, "linear_e4m3: %d images of %d tokens in groups of %d exceed M=%d rows", n_img, tokens, group, M);
   }
-  ssp2_engine e;
-  e.stream = (hipStream_t)hip_stream; e.n_cu = op_cu_count(); e.dev = cur_device();
-  { const char* v = getenv("SSP2_NT_STORES"); e.opt[SSP2_OPT_NT_STORES] = (v && *v) ? atoi(v) : 1; }      // the forward's default store policy
-  e.opt[SSP2_OPT_ZIGZAG] = 1; e.zig = rev;           // the forward alternates the tile walk: next_dir() hands the launch this direction
-  GemmArgs g{};
-  g.A = (const bf16*)a_dev; g.lda = lda; g.W = (const bf16*)w_dev; g.ldw = ldw; g.bias = bias_dev;
-  g.wscale = wscale_dev; g.ascale = ascale_dev; g.ascale_const = ascale_const;
-  g.M = M; g.N = N; g.K = K;
+  if (int rc = check_linear_out("linear_e4m3", epilogue, out_dev, ldo, epilogue == SSP2_EPI_GELU ? 16 : 8, x_dev, ldx, N)) return rc;      // (GELU: e4m3 bytes out, ldo in bytes)
+  ssp2_engine e = op_engine(hip_stream, rev);
+  GemmArgs g = gemm_operands(act_e4m3(a_dev, lda, ascale_dev, ascale_const), w_dev, ldw, wscale_dev, bias_dev, M, N, K, 0);
   g.out = (bf16*)out_dev; g.ldo = ldo; g.x = x_dev; g.xin = xin_dev; g.ldx = ldx;
-  switch (epilogue) {
-    case SSP2_EPI_BF16:
-      if (!out_dev || ldo < N || (ldo % 8)) return fail(SSP2_EINVAL, "linear_e4m3: out / ldo");
-      return launch_gemm256<EPI_BF16, 0, true>(&e, g, -2);
-    case SSP2_EPI_GELU:      // e4m3 bytes out, ldo in bytes
-      if (!out_dev || ldo < N || (ldo % 16)) return fail(SSP2_EINVAL, "linear_e4m3: out / ldo (bytes, a multiple of 16)");
-      if (!score_site) return launch_gemm256<EPI_FC1, 0, true>(&e, g, -2);
-      g.score_site = score_site; g.tokens = tokens; g.slab = slab_dev; g.slab_ld = slab_ld; g.n_img = n_img;
-      { const RowMap rm = make_rowmap(tokens, n_img, group); g.group = rm.group; g.mpad = rm.mpad; }
-      return score_site == 1 ? launch_gemm256<EPI_FC1, 1, true>(&e, g, -2) : launch_gemm256<EPI_FC1, 2, true>(&e, g, -2);
-    case SSP2_EPI_RESID:
-      if (!x_dev || ldx < N || (ldx % 4)) return fail(SSP2_EINVAL, "linear_e4m3: x / ldx");
-      return launch_gemm256<EPI_RESID, 0, true>(&e, g, -2);
-    default: return fail(SSP2_EINVAL, "unknown epilogue %d", epilogue);
+  if (score_site) {
+    const RowMap rm = make_rowmap(tokens, n_img, group);
+    g.score_site = score_site; g.tokens = tokens; g.slab = slab_dev; g.slab_ld = slab_ld; g.n_img = n_img; g.group = rm.group; g.mpad = rm.mpad;
   }
+  return dispatch_gemm(&e, epilogue, true, g, -2);
 }
 
 // The weight quantiser on its own: what quantise_mat launches (quant_rows_e4m3_kernel), on caller-owned buffers.
@@ -1685,25 +1738,18 @@ int ssp2_attention_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int to
                         const uint16_t* q_cls_dev, uint16_t* out_dev, int ldo, uint8_t* out8_dev, int ldo8, float out8_scale,
                         unsigned int* sat_dev, int persist, int live, int rev) {
   if (!qkv_dev) return fail(SSP2_EINVAL, "attention: null qkv");
-  if (n <= 0 || heads <= 0 || tokens <= 0 || group < 0) return fail(SSP2_EINVAL, "attention: n=%d heads=%d tokens=%d group=%d", n, heads, tokens, group);
+  if (int rc = check_attn_args("attention", n, tokens, heads, d_h, group, out_dev, ldo)) return rc;
   if (!attn_supported(d_h, tokens)) return fail(SSP2_EINVAL, "attention kernel not instantiated for d_h=%d, tokens=%d", d_h, tokens);
-  if ((long)heads * d_h > (1 << 20) || (heads * d_h) % 8) return fail(SSP2_EINVAL, "attention: dim = heads * d_h = %ld (a multiple of 8)", (long)heads * d_h);
   const int dim = heads * d_h;
   if (persist < -1 || persist > 1 || live < -1 || live > 1 || rev < 0 || rev > 1) return fail(SSP2_EINVAL, "attention: persist=%d live=%d rev=%d", persist, live, rev);
   if (!out_dev && !out8_dev) return fail(SSP2_EINVAL, "attention: no output");
-  if (out_dev && (ldo < dim || ldo % 8)) return fail(SSP2_EINVAL, "attention: ldo=%d (>= dim %d, a multiple of 8)", ldo, dim);
   if (q_cls_dev && (out8_dev || !out_dev)) return fail(SSP2_EINVAL, "attention: the CLS-only form writes bf16 only");
   if (out8_dev && (ldo8 < dim || ldo8 % 16 || !(out8_scale > 0.f) || out8_scale > 65536.f)) return fail(SSP2_EINVAL, "attention: ldo8=%d out8_scale=%g", ldo8, out8_scale);
-  if ((long)n * heads > 0x7fffffffL) return fail(SSP2_EINVAL, "too many attention items");
-  ssp2_engine e;
-  e.d.dim = dim; e.d.heads = heads; e.tokens = tokens; e.dh = d_h;
+  if (out8_dev && !attn_persistent_for(0, persist < 0 ? 1 : persist, d_h, tokens))
+    return fail(SSP2_EINVAL, "attention: the e4m3 output needs a persistent kernel (d_h = 64 with 97..224 tokens, d_h = 80 with 257)");
+  ssp2_engine e = op_attn_engine(hip_stream, rev, tokens, heads, d_h, qkv_dev, q_cls_dev, out_dev, out_dev ? ldo : dim);      // (rev: the persistent kernels' walk)
   e.opt[SSP2_OPT_ATTN_PERSIST] = persist < 0 ? 1 : persist;
   e.opt[SSP2_OPT_ATTN_LIVE] = live < 0 ? 1 : live;
-  e.opt[SSP2_OPT_ZIGZAG] = 1; e.zig = rev;           // next_dir() hands the persistent kernels this direction
-  if (out8_dev && !attn_persistent(&e)) return fail(SSP2_EINVAL, "attention: the e4m3 output needs a persistent kernel (d_h = 64 with 97..224 tokens, d_h = 80 with 257)");
-  e.stream = (hipStream_t)hip_stream; e.n_cu = op_cu_count(); e.dev = cur_device();
-  e.qkvbuf = (bf16*)qkv_dev; e.q_cls = (bf16*)q_cls_dev;
-  e.obuf = e.o_cls = (bf16*)out_dev; e.o_ld = out_dev ? ldo : dim;
   e.ld8_dim = ldo8; e.fp8_sat = sat_dev;
   return launch_attn(&e, n, make_rowmap(tokens, n, group), q_cls_dev != nullptr, out8_dev, out8_scale);
 }
@@ -1712,19 +1758,12 @@ int ssp2_attention_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int to
 int ssp2_attention_stream_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
                                const uint16_t* q_cls_dev, uint16_t* out_dev, int ldo) {
   if (!qkv_dev || !out_dev) return fail(SSP2_EINVAL, "attention_stream: null qkv / out");
-  if (n <= 0 || heads <= 0 || group < 0) return fail(SSP2_EINVAL, "attention_stream: n=%d heads=%d group=%d", n, heads, group);
+  if (int rc = check_attn_args("attention_stream", n, tokens, heads, d_h, group, out_dev, ldo)) return rc;
   if (d_h != 64) return fail(SSP2_EINVAL, "attention_stream: d_h=%d (64 only)", d_h);
-  if (tokens <= 0 || tokens > ATTN_STREAM_MAX_TOKENS) return fail(SSP2_EINVAL, "attention_stream: tokens=%d (1..%d)", tokens, ATTN_STREAM_MAX_TOKENS);
-  if ((long)heads * d_h > (1 << 20)) return fail(SSP2_EINVAL, "attention_stream: dim = heads * d_h = %ld", (long)heads * d_h);
-  const int dim = heads * d_h;
-  if (ldo < dim || ldo % 8) return fail(SSP2_EINVAL, "attention_stream: ldo=%d (>= dim %d, a multiple of 8)", ldo, dim);
+  if (tokens > ATTN_STREAM_MAX_TOKENS) return fail(SSP2_EINVAL, "attention_stream: tokens=%d (1..%d)", tokens, ATTN_STREAM_MAX_TOKENS);
   if ((long)n * heads * ((tokens + 32 * ATTN_STREAM_QW - 1) / (32 * ATTN_STREAM_QW)) > 0x7fffffffL) return fail(SSP2_EINVAL, "too many attention items");
-  ssp2_engine e;
-  e.d.dim = dim; e.d.heads = heads; e.tokens = tokens; e.dh = d_h;
+  ssp2_engine e = op_attn_engine(hip_stream, -1, tokens, heads, d_h, qkv_dev, q_cls_dev, out_dev, ldo);
   e.opt[SSP2_OPT_ATTN_STREAM] = 2;
-  e.stream = (hipStream_t)hip_stream; e.n_cu = op_cu_count(); e.dev = cur_device();
-  e.qkvbuf = (bf16*)qkv_dev; e.q_cls = (bf16*)q_cls_dev;
-  e.obuf = e.o_cls = (bf16*)out_dev; e.o_ld = ldo;
   return launch_attn_stream(&e, n, make_rowmap(tokens, n, group), q_cls_dev != nullptr);
 }
 
@@ -1733,23 +1772,16 @@ int ssp2_attention_stream_bf16(void* hip_stream, const uint16_t* qkv_dev, int n,
 int ssp2_attention_prefix_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
                                const uint16_t* q_dev, uint16_t* out_dev, int ldo, int n_prefix, int stream) {
   if (!qkv_dev || !q_dev || !out_dev) return fail(SSP2_EINVAL, "attention_prefix: null qkv / q / out");
-  if (n <= 0 || heads <= 0 || tokens <= 0 || group < 0) return fail(SSP2_EINVAL, "attention_prefix: n=%d heads=%d tokens=%d group=%d", n, heads, tokens, group);
+  if (int rc = check_attn_args("attention_prefix", n, tokens, heads, d_h, group, out_dev, ldo)) return rc;
   if (n_prefix < 1 || n_prefix > 2) return fail(SSP2_EINVAL, "attention_prefix: n_prefix=%d (1 or 2)", n_prefix);
   if (n_prefix > tokens) return fail(SSP2_EINVAL, "attention_prefix: n_prefix=%d > tokens=%d", n_prefix, tokens);
   if (stream < 0 || stream > 1) return fail(SSP2_EINVAL, "attention_prefix: stream=%d (0 resident, 1 key-streaming)", stream);
   if (stream ? !attn_stream_ok(d_h, tokens) : !attn_resident(d_h, tokens))
     return fail(SSP2_EINVAL, "attention_prefix: no %s kernel for d_h=%d, tokens=%d", stream ? "key-streaming" : "resident", d_h, tokens);
-  if ((long)heads * d_h > (1 << 20) || (heads * d_h) % 8) return fail(SSP2_EINVAL, "attention_prefix: dim = heads * d_h = %ld (a multiple of 8)", (long)heads * d_h);
-  const int dim = heads * d_h;
-  if (ldo < dim || ldo % 8) return fail(SSP2_EINVAL, "attention_prefix: ldo=%d (>= dim %d, a multiple of 8)", ldo, dim);
-  if ((long)n * heads > 0x7fffffffL || (long)n_prefix * n * ldo > 0x7fffffffL || (long)n * dim > 0x7fffffffL)
-    return fail(SSP2_EINVAL, "attention_prefix: n=%d too large", n);
-  ssp2_engine e;
-  e.d.dim = dim; e.d.heads = heads; e.tokens = tokens; e.dh = d_h; e.tail_rows = n_prefix;
+  if ((long)n_prefix * n * ldo > 0x7fffffffL || (long)n * heads * d_h > 0x7fffffffL) return fail(SSP2_EINVAL, "attention_prefix: n=%d too large", n);
+  ssp2_engine e = op_attn_engine(hip_stream, -1, tokens, heads, d_h, qkv_dev, q_dev, out_dev, ldo);
+  e.tail_rows = n_prefix;
   e.opt[SSP2_OPT_ATTN_STREAM] = stream ? 2 : 0;
-  e.stream = (hipStream_t)hip_stream; e.n_cu = op_cu_count(); e.dev = cur_device();
-  e.qkvbuf = (bf16*)qkv_dev; e.q_cls = (bf16*)q_dev;
-  e.obuf = e.o_cls = (bf16*)out_dev; e.o_ld = ldo;
   return launch_attn(&e, n, make_rowmap(tokens, n, group), true);
 }
 
@@ -1765,11 +1797,8 @@ int ssp2_layernorm(void* hip_stream, const float* x_dev, size_t in_stride, int r
   if (!y_dev == !y8_dev) return fail(SSP2_EINVAL, "layernorm: exactly one of y (bf16) and y8 (e4m3) is written");
   if (y8_dev && !ascale_dev) return fail(SSP2_EINVAL, "layernorm: the e4m3 form writes per-row scales (ascale)");
   if (out_ld < D || out_ld % 4) return fail(SSP2_EINVAL, "layernorm: out_ld=%d (>= D, a multiple of 4)", out_ld);
-  ssp2_engine e;
+  ssp2_engine e = op_engine(hip_stream, rev);
   e.d.ln_eps = eps;
-  e.opt[SSP2_OPT_BIG_TILE_MIN_ROWS] = kBigTileMinRowsDefault;
-  e.opt[SSP2_OPT_ZIGZAG] = 1; e.zig = rev;
-  e.stream = (hipStream_t)hip_stream; e.dev = cur_device();
   const RowMap gather = gather_tokens > 0 ? make_rowmap(gather_tokens, rows, gather_group) : RowMap{0, 0, 0};
   return launch_ln(&e, x_dev, in_stride, gamma_dev, beta_dev, (bf16*)y_dev, out_ld, rows, D, gather, y8_dev, y8_dev ? ascale_dev : nullptr);
 }
