@@ -198,6 +198,17 @@ __device__ __forceinline__ void ln_row_finish(const f32x4 (&v)[MAXV], int lane, 
     if (FULL || i * 64 + lane < nv) ln_chunk_write<OUT8>(v[i], mean, rstd, g4[i], b4[i], y, i * 64 + lane);
 }
 
+// LayerScale on a residual branch (timm Block.ls1 / ls2 under autocast): the branch output y is bf16, gamma an fp32 parameter, so
+// gamma * y is ONE fp32 product and the residual add a SECOND fp32 operation: x + fl32(gamma * y).  Two roundings — a fused
+// multiply-add (one rounding) gives other bits, so contraction stays off for this pair in both GEMM kernels' epilogues.
+__device__ __forceinline__ f32x4 ls_scale_add(const f32x4& x, const f32x4& gamma, const f32x4& y) {
+#pragma clang fp contract(off)
+  f32x4 r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { const float p = gamma[k] * y[k]; r[k] = x[k] + p; }
+  return r;
+}
+
 // XCD-aware bijective remap of a 1-D grid (blocks b and b+8 share an XCD): each XCD walks a contiguous
 // range of logical tile ids, so neighbours that share an operand panel hit the same 4 MiB L2.
 __device__ __forceinline__ int xcd_remap(int bid, int nblk) {

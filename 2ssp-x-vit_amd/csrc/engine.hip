@@ -85,7 +85,18 @@ struct Layer {
   bool attn_dropped = false;   // ssp2_drop_attention: bypass for good
   float o8_scale = ATTN_OUT8_SCALE;   // fp8 mode: the attention output of this block is handed to the out-projection as e4m3(o * o8_scale)
   int* keep_dev = nullptr;     // ssp2_prune_ffn_into: the kept-neuron list on the device
+  // LayerScale (ssp2_set_layer_scale): fp32 [dim] per residual branch, [0] attention (timm ls1), [1] MLP (ls2); a branch whose scale
+  // was set runs EPI_RESID_LS, any other EPI_RESID.  The storage (2 x ceil256(dim) floats per block) comes out of ssp2_create's arena, so
+  // that setting a scale inside a caller's prune bracket is one small copy: no allocation, no memset
+  float* ls[2] = {nullptr, nullptr};
+  bool ls_set[2] = {false, false};
 };
+// the residual epilogue of block L's branch (0 attention, 1 MLP): with its LayerScale when one was set
+static inline int resid_epi(const Layer& L, int branch, GemmArgs& g) {
+  if (!L.ls_set[branch]) return EPI_RESID;
+  g.ls = L.ls[branch];
+  return EPI_RESID_LS;
+}
 // everything a block's attention half / MLP half reads has been loaded (the block loop and the tail ask before they launch)
 static inline bool attn_loaded(const Layer& L) { return L.ln_set[0] && L.ln_set[1] && L.qkv.w_set && L.qkv.b_set && L.proj.w_set && L.proj.b_set; }
 static inline bool mlp_loaded(const Layer& L) { return L.ln_set[2] && L.ln_set[3] && L.fc1.w_set && L.fc1.b_set && L.fc2.w_set && L.fc2.b_set; }
@@ -247,7 +258,7 @@ static int launch_gemm256(ssp2_engine* e, GemmArgs g, int klass) {
   if (F8 && (g.K % 128 || !g.wscale)) return fail(SSP2_EINVAL, "fp8 GEMM needs K %% 128 == 0 and per-row weight scales (K=%d)", g.K);
   static bool attr_done[kMaxDevices] = {};
   if (!attr_done[e->dev]) {
-    HIPCHK(hipFuncSetAttribute((const void*)gemm256_bf16_kernel<EPI, SCORE, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, G256::LDS));
+    HIPCHK(hipFuncSetAttribute((const void*)gemm256_entry<EPI, SCORE, F8>(), hipFuncAttributeMaxDynamicSharedMemorySize, G256::LDS));
     attr_done[e->dev] = true;
   }
   g.nt_out = e->opt[SSP2_OPT_NT_STORES];
@@ -259,7 +270,7 @@ static int launch_gemm256(ssp2_engine* e, GemmArgs g, int klass) {
   }
   ProfScope ps(e, klass, 2.0 * g.M * (double)g.N * g.K);
   const int wgs = std::min(g.tiles_m * g.tiles_n, e->n_cu);
-  hipLaunchKernelGGL((gemm256_bf16_kernel<EPI, SCORE, F8>), dim3(wgs), dim3(512), G256::LDS, e->stream, g);
+  hipLaunchKernelGGL((gemm256_entry<EPI, SCORE, F8>()), dim3(wgs), dim3(512), G256::LDS, e->stream, g);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -319,7 +330,7 @@ static int launch_gemm_small(ssp2_engine* e, GemmArgs g, int klass);
 template <int EPI, int SCORE = 0>
 static int launch_gemm(ssp2_engine* e, GemmArgs g, int klass) {
   if (g.K % GEMM_BK) return fail(SSP2_EINVAL, "GEMM K=%d not a multiple of %d", g.K, GEMM_BK);
-  if constexpr (EPI == EPI_BF16 || EPI == EPI_RESID || EPI == EPI_FC1) {
+  if constexpr (EPI == EPI_BF16 || EPI == EPI_RESID || EPI == EPI_RESID_LS || EPI == EPI_FC1) {
     if (g.M >= big_tile_min_rows(e) && !(EPI == EPI_FC1 && (g.out2 || !e->opt[SSP2_OPT_FC1_BIG_TILES])) && e->opt[SSP2_OPT_BIG_TILES]) {
 #ifdef SSP2_LAB
       if constexpr (EPI == EPI_RESID && SCORE == 0) {      // the deferred residual (same bits): full column tiles, a main loop long enough to ride on
@@ -398,6 +409,7 @@ static int dispatch_gemm(ssp2_engine* e, int epi, bool f8, const GemmArgs& g, in
   if (epi == EPI_BF16 && !site && !lnv) return GEMM_FORM(EPI_BF16, 0);
   if (epi == EPI_RESID && !site && lnv) return f8 ? launch_resid_ln<true>(e, g, lnv, klass) : launch_resid_ln<false>(e, g, lnv, klass);
   if (epi == EPI_RESID && !site) return GEMM_FORM(EPI_RESID, 0);
+  if (epi == EPI_RESID_LS && !site && !lnv && g.ls) return GEMM_FORM(EPI_RESID_LS, 0);     // (no lab form behind it: see attn_half / mlp_half)
   if (epi == EPI_FC1 && !lnv && site == 1) return GEMM_FORM(EPI_FC1, 1);
   if (epi == EPI_FC1 && !lnv && site == 2) return GEMM_FORM(EPI_FC1, 2);
   if (epi == EPI_FC1 && !lnv && site == 0) return GEMM_FORM(EPI_FC1, 0);
@@ -714,6 +726,7 @@ int ssp2_create_ext(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_vi
     e->ld_int_max = L.ld_int > e->ld_int_max ? L.ld_int : e->ld_int_max;
     TRYA(dalloc(e, &L.ln1_g, d.dim, false)); TRYA(dalloc(e, &L.ln1_b, d.dim, false));
     TRYA(dalloc(e, &L.ln2_g, d.dim, false)); TRYA(dalloc(e, &L.ln2_b, d.dim, false));
+    TRYA(dalloc(e, &L.ls[0], (size_t)ceil_to(d.dim, 256), false)); TRYA(dalloc(e, &L.ls[1], (size_t)ceil_to(d.dim, 256), false));      // (padded like a bias, pad zero)
     TRYA(mat_alloc(e, L.qkv, 3 * d.dim, d.dim));
     TRYA(mat_alloc(e, L.proj, d.dim, d.dim));
     TRYA(mat_alloc(e, L.fc1, L.d_int, d.dim));
@@ -1042,6 +1055,22 @@ int ssp2_load_tensors_dev(ssp2_handle e, int count, const int* kinds, const int*
   return 0;
 }
 
+// LayerScale of one residual branch: fp32 in, fp32 held (the parameter is never rounded: autocast multiplies by it in fp32)
+static int set_layer_scale_impl(ssp2_engine* e, Layer& L, int branch, const float* gamma, bool dev) {
+  const int D = e->d.dim;
+  HIPCHK(hipMemcpyAsync(L.ls[branch], gamma, (size_t)D * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+  if (!dev) HIPCHK(hipStreamSynchronize(e->stream));
+  L.ls_set[branch] = true;
+  return 0;
+}
+int ssp2_set_layer_scale(ssp2_handle e, int layer, int branch, const float* gamma, int on_device) {
+  if (!e) return fail(SSP2_EINVAL, "null handle");
+  if (layer < 0 || layer >= e->d.depth) return fail(SSP2_EINVAL, "set_layer_scale: layer %d out of range [0, %d)", layer, e->d.depth);
+  if (branch < 0 || branch > 1) return fail(SSP2_EINVAL, "set_layer_scale: branch %d (0 = attention, 1 = MLP)", branch);
+  if (!gamma) return fail(SSP2_EINVAL, "set_layer_scale: null gamma");
+  return set_layer_scale_impl(e, e->layers[layer], branch, gamma, on_device != 0);
+}
+
 static int check_n(ssp2_engine* e, int n, int group = 0) {
   if (!e) return fail(SSP2_EINVAL, "null handle");
   if (n <= 0 || n > e->d.max_images) return fail(SSP2_ESTATE, "n=%d outside (0, max_images=%d]", n, e->d.max_images);
@@ -1213,9 +1242,11 @@ static int attn_half(ssp2_engine* e, LayersCall& c, int l) {
   }
   GemmArgs p = bind(L.proj, f8_proj ? act_e4m3(e->obuf8, e->ld8_dim, nullptr, 1.0f / L.o8_scale) : act_bf16(e->obuf, D), M, D);
   p.x = c.x; p.ldx = D; p.xin = c.xsrc;
-  const int lnv = ln_fusable(e, M, D, f8_proj);        // + LN2 of this layer: fc1's operand
+  // a branch with LayerScale takes the product form only: the lab forms (LayerNorm behind the epilogue, deferred residual) know no scale
+  const int epi = resid_epi(L, 0, p);
+  const int lnv = epi == EPI_RESID ? ln_fusable(e, M, D, f8_proj) : 0;        // + LN2 of this layer: fc1's operand
   if (lnv) fuse_ln_to_hbuf(e, p, L.ln2_g, L.ln2_b, c.f8_fc1);
-  if ((rc = dispatch_gemm(e, EPI_RESID, f8_proj, p, SSP2_K_GEMM_PROJ, lnv))) return rc;
+  if ((rc = dispatch_gemm(e, epi, f8_proj, p, SSP2_K_GEMM_PROJ, lnv))) return rc;
   c.h_ready = lnv != 0;
   c.xsrc = c.x;
   return 0;
@@ -1282,9 +1313,11 @@ static int mlp_half(ssp2_engine* e, LayersCall& c, int l) {
   if (c.scores_only && l + 1 == c.l_end) return 0;            // nothing reads x behind the last hooked activation
   GemmArgs o = bind(L.fc2, f8 ? act_e4m3(e->act8, ld8_int, nullptr) : act_bf16(e->actbuf, L.ld_int), M, D);
   o.x = c.x; o.ldx = D; o.xin = c.xsrc;
+  const int epi = resid_epi(L, 1, o);
   // + the LayerNorm the NEXT layer of this call starts with: LN1 of layer l + 1, or its LN2 when its attention is skipped
+  // (not behind a LayerScale epilogue: product form only)
   int lnv = 0;
-  if (l + 1 < c.l_end) {
+  if (l + 1 < c.l_end && epi == EPI_RESID) {
     const Layer& Ln = e->layers[l + 1];
     const bool skip_n = attn_skipped(e, c, l + 1);
     if (skip_n ? (Ln.ln_set[2] && Ln.ln_set[3]) : (Ln.ln_set[0] && Ln.ln_set[1])) {
@@ -1292,7 +1325,7 @@ static int mlp_half(ssp2_engine* e, LayersCall& c, int l) {
       if (lnv) fuse_ln_to_hbuf(e, o, skip_n ? Ln.ln2_g : Ln.ln1_g, skip_n ? Ln.ln2_b : Ln.ln1_b, skip_n ? c.f8_fc1 : c.f8);
     }
   }
-  if ((rc = dispatch_gemm(e, EPI_RESID, f8, o, SSP2_K_GEMM_FC2, lnv))) return rc;
+  if ((rc = dispatch_gemm(e, epi, f8, o, SSP2_K_GEMM_FC2, lnv))) return rc;
   c.h_ready = lnv != 0;
   c.xsrc = c.x;
   return 0;
@@ -1447,7 +1480,7 @@ int ssp2_tail_group(ssp2_handle e, const float* x, int n_slot, int slots, int gr
     if ((rc = launch_attn(e, n, rm, true))) return rc;
     GemmArgs p = bind(L.proj, act_bf16(e->o_cls, D), PN, D);
     p.x = e->x_cls; p.ldx = D;
-    if ((rc = dispatch_gemm(e, EPI_RESID, false, p, SSP2_K_GEMM_PROJ))) return rc;
+    if ((rc = dispatch_gemm(e, resid_epi(L, 0, p), false, p, SSP2_K_GEMM_PROJ))) return rc;
   }
   if ((rc = launch_ln(e, e->x_cls, D, L.ln2_g, L.ln2_b, e->h_cls, D, PN, D))) return rc;
   GemmArgs f = bind(L.fc1, act_bf16(e->h_cls, D), PN, L.ld_int);
@@ -1455,7 +1488,7 @@ int ssp2_tail_group(ssp2_handle e, const float* x, int n_slot, int slots, int gr
   if ((rc = dispatch_gemm(e, EPI_FC1, false, f, SSP2_K_GEMM_FC1))) return rc;
   GemmArgs o = bind(L.fc2, act_bf16(e->act_cls, L.ld_int), PN, D);
   o.x = e->x_cls; o.ldx = D;
-  if ((rc = dispatch_gemm(e, EPI_RESID, false, o, SSP2_K_GEMM_FC2))) return rc;
+  if ((rc = dispatch_gemm(e, resid_epi(L, 1, o), false, o, SSP2_K_GEMM_FC2))) return rc;
   return head_impl(e, e->x_cls, (size_t)D, n, logits_dev, pred, labels, correct, RowMap{0, 0, 0}, period, true);
 }
 
@@ -1585,6 +1618,10 @@ int ssp2_clone_weights(ssp2_handle dst, ssp2_handle src) {
     if ((rc = copy_mat(dst, d.qkv, s.qkv)) || (rc = copy_mat(dst, d.proj, s.proj))) return rc;
     d.attn_dropped = s.attn_dropped;
     d.o8_scale = s.o8_scale;
+    for (int br = 0; br < 2; ++br) {      // LayerScale is per hidden column: width pruning leaves it alone
+      if (s.ls_set[br]) { if ((rc = set_layer_scale_impl(dst, d, br, s.ls[br], true))) return rc; }
+      else d.ls_set[br] = false;
+    }
     if (d.d_int == s.d_int) { if ((rc = copy_mat(dst, d.fc1, s.fc1)) || (rc = copy_mat(dst, d.fc2, s.fc2))) return rc; }
     else {   // the FFN arrives through ssp2_prune_ffn_into; fc2's bias does not depend on the kept neurons
       HIPCHK(hipMemcpyAsync(d.fc2.b, s.fc2.b, (size_t)d.fc2.rows_pad * 4, hipMemcpyDeviceToDevice, dst->stream));
@@ -1719,6 +1756,44 @@ int ssp2_linear_e4m3(void* hip_stream, int epilogue, const uint8_t* a_dev, int l
     g.score_site = score_site; g.tokens = tokens; g.slab = slab_dev; g.slab_ld = slab_ld; g.n_img = n_img; g.group = rm.group; g.mpad = rm.mpad;
   }
   return dispatch_gemm(&e, epilogue, true, g, -2);
+}
+
+// The residual projections with LayerScale on their own (EPI_RESID_LS): the launches of ssp2_linear_bf16 / ssp2_linear_e4m3 with the
+// residual epilogue, plus the branch's fp32 scale.  Every argument is checked before the device is touched.
+int ssp2_linear_ls_bf16(void* hip_stream, const uint16_t* a_dev, int lda, const uint16_t* w_dev, int ldw, const float* bias_dev,
+                        const float* gamma_dev, int M, int N, int K, float* x_dev, const float* xin_dev, int ldx, int kernel, int rev) {
+  if (!a_dev || !w_dev || !bias_dev) return fail(SSP2_EINVAL, "linear_ls: null operand");
+  if (!gamma_dev) return fail(SSP2_EINVAL, "linear_ls: null gamma");
+  if ((uintptr_t)gamma_dev & 15) return fail(SSP2_EINVAL, "linear_ls: gamma must be 16-byte aligned (the epilogues read it four columns at a time)");
+  if (M <= 0 || N <= 0 || K <= 0 || (K % GEMM_BK) || (N % 64)) return fail(SSP2_EINVAL, "linear_ls: M=%d N=%d K=%d (K multiple of %d, N multiple of 64)", M, N, K, GEMM_BK);
+  if (lda < K || ldw < K || (lda % 8) || (ldw % 8)) return fail(SSP2_EINVAL, "linear_ls: lda=%d ldw=%d must be >= K and multiples of 8", lda, ldw);
+  if (kernel < 0 || kernel > 2) return fail(SSP2_EINVAL, "linear_ls: kernel selector %d", kernel);
+  if (rev < 0 || rev > 1) return fail(SSP2_EINVAL, "linear_ls: rev=%d", rev);
+  if (int rc = check_linear_out("linear_ls", SSP2_EPI_RESID, nullptr, 0, 8, x_dev, ldx, N)) return rc;
+  ssp2_engine e = op_engine(hip_stream, rev);
+  if (kernel == 1) e.opt[SSP2_OPT_BIG_TILES] = 0;
+  if (kernel == 2) e.opt[SSP2_OPT_BIG_TILE_MIN_ROWS] = 1;
+  GemmArgs g = gemm_operands(act_bf16((const bf16*)a_dev, lda), w_dev, ldw, nullptr, bias_dev, M, N, K, ceil_to(N, 256) / GEMM_BN);
+  g.x = x_dev; g.xin = xin_dev; g.ldx = ldx; g.ls = gamma_dev;
+  return dispatch_gemm(&e, EPI_RESID_LS, false, g, -2);
+}
+int ssp2_linear_ls_e4m3(void* hip_stream, const uint8_t* a_dev, int lda, const float* ascale_dev, float ascale_const, const uint8_t* w_dev, int ldw,
+                        const float* wscale_dev, const float* bias_dev, const float* gamma_dev, int M, int N, int K, float* x_dev,
+                        const float* xin_dev, int ldx, int rev) {
+  if (!a_dev || !w_dev || !bias_dev) return fail(SSP2_EINVAL, "linear_ls_e4m3: null operand");
+  if (!gamma_dev) return fail(SSP2_EINVAL, "linear_ls_e4m3: null gamma");
+  if ((uintptr_t)gamma_dev & 15) return fail(SSP2_EINVAL, "linear_ls_e4m3: gamma must be 16-byte aligned (the epilogues read it four columns at a time)");
+  if (rev < 0 || rev > 1) return fail(SSP2_EINVAL, "linear_ls_e4m3: rev=%d", rev);
+  if (!wscale_dev) return fail(SSP2_EINVAL, "linear_ls_e4m3: the weight rows' scales (wscale) are required");
+  if (M <= 0 || N <= 0 || K <= 0 || (K % 128) || (N % 64)) return fail(SSP2_EINVAL, "linear_ls_e4m3: M=%d N=%d K=%d (K multiple of 128, N multiple of 64)", M, N, K);
+  if (lda < K || ldw < K || (lda % 16) || (ldw % 16)) return fail(SSP2_EINVAL, "linear_ls_e4m3: lda=%d ldw=%d must be >= K and multiples of 16", lda, ldw);
+  if (!std::isfinite(ascale_const) || ascale_const < 0.f) return fail(SSP2_EINVAL, "linear_ls_e4m3: ascale_const=%g", ascale_const);
+  if (ascale_dev && ascale_const != 0.f) return fail(SSP2_EINVAL, "linear_ls_e4m3: per-row ascale and ascale_const are exclusive");
+  if (int rc = check_linear_out("linear_ls_e4m3", SSP2_EPI_RESID, nullptr, 0, 8, x_dev, ldx, N)) return rc;
+  ssp2_engine e = op_engine(hip_stream, rev);
+  GemmArgs g = gemm_operands(act_e4m3(a_dev, lda, ascale_dev, ascale_const), w_dev, ldw, wscale_dev, bias_dev, M, N, K, 0);
+  g.x = x_dev; g.xin = xin_dev; g.ldx = ldx; g.ls = gamma_dev;
+  return dispatch_gemm(&e, EPI_RESID_LS, true, g, -2);
 }
 
 // The weight quantiser on its own: what quantise_mat launches (quant_rows_e4m3_kernel), on caller-owned buffers.

@@ -22,10 +22,12 @@
 //              per-(sample, neuron) partial sum of squares over this tile's tokens -> slab (2 segments/tile)
 //   EPI_PATCH  x[img*N + P + p] = float(bf16(acc + bias)) + pos[P + p]  patch-embed conv as GEMM (P = prefix tokens: CLS [+ DIST])
 //   EPI_F32    out_f32 = float(bf16(acc + bias))                        classifier head (tiny, scalar stores)
+//   EPI_RESID_LS  x = xin + fl32(ls[n] * float(bf16(acc + bias)))         EPI_RESID with LayerScale: the branch's per-column fp32 scale,
+//              product and sum rounded separately (common.hip.h ls_scale_add)
 #pragma once
 #include "common.hip.h"
 
-enum { EPI_BF16 = 0, EPI_RESID = 1, EPI_FC1 = 2, EPI_PATCH = 3, EPI_F32 = 4 };
+enum { EPI_BF16 = 0, EPI_RESID = 1, EPI_FC1 = 2, EPI_PATCH = 3, EPI_F32 = 4, EPI_RESID_LS = 5 };
 
 #define GEMM_BM 128
 #define GEMM_BN 128
@@ -72,6 +74,7 @@ struct GemmArgs {
   // Deferred residual (gemm256 kernel, EPI_RESID with SCORE = 1): per workgroup 256 x 256 bf16 (128 KiB) where a tile's
   // bf16(acc + bias) is parked until the NEXT tile's main loop adds it to x (see gemm256.hip.h, DG); [gridDim.x][8 waves][16 KiB]
   unsigned int* dg;
+  const float* ls;            // EPI_RESID_LS: the residual branch's LayerScale, fp32 [N] (kept as loaded, never rounded)
 #ifdef GEMM_STAMPS
   unsigned long long* stamps; // diagnostic build only: [blocks][64] s_memtime values of wave 0
 #endif
@@ -405,8 +408,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs g) {
     return;
   }
 
-  // EPI_RESID / EPI_PATCH: fp32 staging [64][64] per wave, then float4 read-modify-write of x
+  // EPI_RESID / EPI_RESID_LS / EPI_PATCH: fp32 staging [64][64] per wave, then float4 read-modify-write of x
   {
+    constexpr bool LS = EPI == EPI_RESID_LS;
     char* stg = smem + wave * 16384;
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -422,13 +426,15 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs g) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (!wave_cols_ok) return;
     const int c = (lane & 15) * 4;
+    f32x4 gm = {1.f, 1.f, 1.f, 1.f};         // LS: the scales of this lane's four columns, the same in every row it writes
+    if constexpr (LS) gm = *(const f32x4*)(g.ls + col0 + c);
     f32x4 xin[16];
     float* dst[16];
 #pragma unroll
     for (int it = 0; it < 16; ++it) {
       const int m = row0 + it * 4 + (lane >> 4);
       const int mc = m < g.M ? m : g.M - 1;
-      if (EPI == EPI_RESID) {
+      if (EPI == EPI_RESID || LS) {
         dst[it] = g.x + (size_t)mc * g.ldx + col0 + c;
         xin[it] = *(const f32x4*)((g.xin ? g.xin : g.x) + (size_t)mc * g.ldx + col0 + c);
       } else {
@@ -442,7 +448,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs g) {
     for (int it = 0; it < 16; ++it) {
       const int r = it * 4 + (lane >> 4);
       const f32x4 v = *(const f32x4*)(stg + r * 256 + c * 4);
-      if (row0 + r < g.M) *(f32x4*)dst[it] = xin[it] + v;
+      if (row0 + r < g.M) *(f32x4*)dst[it] = LS ? ls_scale_add(xin[it], gm, v) : xin[it] + v;
     }
   }
 }

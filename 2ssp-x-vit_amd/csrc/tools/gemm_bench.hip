@@ -2,7 +2,9 @@
 //   gemm_bench.bin M N K epi [iters] [tokens]       epi: 0 bf16, 1 resid, 2 fc1(+score), 3 patch, 4 f32 (128x128 kernel);
 //   10/11/12 bf16/resid/fc1 on the persistent 256x256 kernel (13/14: + pre- / post-GELU stage-1 score),
 //   15 resid + fused LayerNorm of the finished row panels (N = 768 / 1024 / 1280; x vs the 128x128 kernel, h vs layernorm_bf16_kernel),
-//   40/41/42 the same on the four-wave kernel (gemm256w4.hip.h), 30..33 e4m3 operands (gemm256 F8)
+//   40/41/42 the same on the four-wave kernel (gemm256w4.hip.h), 30..33 e4m3 operands (gemm256 F8),
+//   7 / 17 / 37 resid + LayerScale (EPI_RESID_LS) on the 128x128 kernel / the 256x256 kernel (checked bit for bit against 7) / e4m3 operands:
+//   the same shape under 1 / 11 / 31 is the plain residual form it is measured against
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -44,9 +46,9 @@ template <int EPI, int SCORE = 0> static void launch(const GemmArgs& g, hipStrea
 static int nCU = 256;
 template <int EPI, int SCORE = 0> static void launch256(GemmArgs g, hipStream_t s) {
   static bool done = false;
-  if (!done) { CK(hipFuncSetAttribute((const void*)gemm256_bf16_kernel<EPI, SCORE>, hipFuncAttributeMaxDynamicSharedMemorySize, G256::LDS)); done = true; }
+  if (!done) { CK(hipFuncSetAttribute((const void*)gemm256_entry<EPI, SCORE>(), hipFuncAttributeMaxDynamicSharedMemorySize, G256::LDS)); done = true; }
   g.tiles_m = (g.M + 255) / 256; g.tiles_n = (g.N + 255) / 256;
-  hipLaunchKernelGGL((gemm256_bf16_kernel<EPI, SCORE>), dim3(std::min(g.tiles_m * g.tiles_n, nCU)), dim3(512), G256::LDS, s, g);
+  hipLaunchKernelGGL((gemm256_entry<EPI, SCORE>()), dim3(std::min(g.tiles_m * g.tiles_n, nCU)), dim3(512), G256::LDS, s, g);
 }
 template <int LNV> static void launch256ln(GemmArgs g, hipStream_t s) {   // residual + LayerNorm of the finished panels by their last-arriving workgroup
   static bool done = false;
@@ -68,11 +70,11 @@ template <int EPI> static void launch256w4(GemmArgs g, hipStream_t s) {   // fou
 }
 template <int EPI, int SCORE = 0> static void launch256f8(GemmArgs g, hipStream_t s) {   // e4m3 operands (gemm256 with F8 = true)
   static bool done = false;
-  if (!done) { CK(hipFuncSetAttribute((const void*)gemm256_bf16_kernel<EPI, SCORE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G256::LDS)); done = true; }
+  if (!done) { CK(hipFuncSetAttribute((const void*)gemm256_entry<EPI, SCORE, true>(), hipFuncAttributeMaxDynamicSharedMemorySize, G256::LDS)); done = true; }
   g.tiles_m = (g.M + 255) / 256; g.tiles_n = (g.N + 255) / 256;
-  hipLaunchKernelGGL((gemm256_bf16_kernel<EPI, SCORE, true>), dim3(std::min(g.tiles_m * g.tiles_n, nCU)), dim3(512), G256::LDS, s, g);
+  hipLaunchKernelGGL((gemm256_entry<EPI, SCORE, true>()), dim3(std::min(g.tiles_m * g.tiles_n, nCU)), dim3(512), G256::LDS, s, g);
 }
-// epi 30 bf16-out (QKV), 31 resid (fc2), 32 fc1 (+GELU, e4m3 out), 33 fc1 + pre-GELU score (e4m3 out + slab): e4m3 operands.
+// epi 30 bf16-out (QKV), 31 resid (fc2), 32 fc1 (+GELU, e4m3 out), 33 fc1 + pre-GELU score (e4m3 out + slab), 37 resid + LayerScale: e4m3 operands.
 // Operands are quantised on the host (A: direct cast, W: per-row scale amax/448), the reference is the fp32 sum of the
 // exact products of the DEQUANTISED values, so the check isolates the kernel (layout, scale, epilogue) from quantisation.
 static int run_fp8(int M, int N, int K, int epi, int iters, int tokens) {
@@ -88,7 +90,10 @@ static int run_fp8(int M, int N, int K, int epi, int iters, int tokens) {
     for (int k = 0; k < K; ++k) { const uint8_t q = f_to_e4m3(row[k] / sc); hW[(size_t)n * K8 + k] = q; fW[(size_t)n * K8 + k] = e4m3_to_f(q); }
     hb[n] = bf2f(f2bf(0.01f * (n % 13 - 6)));
   }
-  uint8_t *A, *W, *out8; bf16* out; float *bias, *ws, *x, *slab;
+  std::vector<float> hg(Npad, 0.f);
+  for (int n = 0; n < N; ++n) hg[n] = (n % 5 == 3 ? -1.f : 1.f) * (0.25f + (n % 17) / 16.f);      // the LayerScale of epi 37
+  uint8_t *A, *W, *out8; bf16* out; float *bias, *ws, *x, *slab, *ls;
+  CK(hipMalloc(&ls, Npad * 4)); CK(hipMemcpy(ls, hg.data(), Npad * 4, hipMemcpyHostToDevice));
   CK(hipMalloc(&A, hA.size())); CK(hipMalloc(&W, hW.size())); CK(hipMalloc(&out, (size_t)M * Npad * 2)); CK(hipMalloc(&out8, (size_t)M * Npad));
   CK(hipMalloc(&bias, Npad * 4)); CK(hipMalloc(&ws, Npad * 4)); CK(hipMalloc(&x, (size_t)(M + 4) * Npad * 4)); CK(hipMalloc(&slab, (size_t)((M + 127) / 128) * 2 * Npad * 4));
   CK(hipMemcpy(A, hA.data(), hA.size(), hipMemcpyHostToDevice)); CK(hipMemcpy(W, hW.data(), hW.size(), hipMemcpyHostToDevice));
@@ -97,9 +102,9 @@ static int run_fp8(int M, int N, int K, int epi, int iters, int tokens) {
   GemmArgs g{};
   g.A = (const bf16*)A; g.lda = K8; g.W = (const bf16*)W; g.ldw = K8; g.bias = bias; g.wscale = ws; g.M = M; g.N = N; g.K = K8;
   g.out = epi >= 32 ? (bf16*)out8 : out; g.ldo = Npad; g.x = x; g.ldx = Npad; g.tokens = tokens; g.slab = slab; g.slab_ld = Npad;
-  g.score_site = epi == 33 ? 1 : 0;
+  g.score_site = epi == 33 ? 1 : 0; g.ls = ls;
   hipStream_t s; CK(hipStreamCreate(&s));
-  auto run = [&]() { switch (epi) { case 30: launch256f8<EPI_BF16>(g, s); break; case 31: launch256f8<EPI_RESID>(g, s); break;
+  auto run = [&]() { switch (epi) { case 30: launch256f8<EPI_BF16>(g, s); break; case 31: launch256f8<EPI_RESID>(g, s); break; case 37: launch256f8<EPI_RESID_LS>(g, s); break;
                                     case 32: launch256f8<EPI_FC1, 0>(g, s); break; case 33: launch256f8<EPI_FC1, 1>(g, s); break; } };
   run(); CK(hipStreamSynchronize(s));
   // reference on a sample of rows (all columns): full check is M*N*K host flops
@@ -116,11 +121,11 @@ static int run_fp8(int M, int N, int K, int epi, int iters, int tokens) {
       const float sumtol = (float)(4e-6 * mag * hs[n]);          // accumulation error where the terms cancel (the scaled MFMA aligns the products of a 64-deep step before adding: ~2e-6 of sum|terms| measured)
       ++checked;
       if (epi == 30) { const float got = bf2f(ho[(size_t)m * Npad + n]); const float d = fabsf(got - pre); const float tol = fabsf(pre) * 0.0079f + sumtol + 1e-6f; if (d > tol) { if (bad < 8) printf("  out[%d][%d] = %g, ref %g\n", m, n, got, pre); ++bad; } maxrel = std::max(maxrel, (double)d / (fabsf(pre) + 1e-3)); }
-      else if (epi == 31) { const float got = hx[(size_t)m * Npad + n]; const float d = fabsf(got - pre); const float tol = fabsf(pre) * 0.0079f + sumtol + 1e-6f; if (d > tol) { if (bad < 8) printf("  x[%d][%d] = %g, ref %g\n", m, n, got, pre); ++bad; } maxrel = std::max(maxrel, (double)d / (fabsf(pre) + 1e-3)); }
+      else if (epi == 31 || epi == 37) { const float gm = epi == 37 ? hg[n] : 1.f; const float got = hx[(size_t)m * Npad + n]; const float d = fabsf(got - gm * pre); const float tol = fabsf(gm) * (fabsf(pre) * 0.0079f + sumtol) + 1e-6f; if (d > tol) { if (bad < 8) printf("  x[%d][%d] = %g, ref %g\n", m, n, got, pre); ++bad; } maxrel = std::max(maxrel, (double)d / (fabsf(pre) + 1e-3)); }
       else { const float ge = bf2f(f2bf(0.5f * pre * (1.f + erff(pre * 0.70710678f)))); const float got = e4m3_to_f(ho8[(size_t)m * Npad + n]);
              const float d = fabsf(got - ge); const float tol = fabsf(ge) * 0.13f + 0.004f; if (d > tol) { if (bad < 8) printf("  act8[%d][%d] = %g, ref gelu %g (pre %g)\n", m, n, got, ge, pre); ++bad; } }
     }
-  if (epi == 31) { for (size_t i = (size_t)M * Npad; i < hx.size(); ++i) if (hx[i] != 0.f) { ++bad; } }
+  if (epi == 31 || epi == 37) { for (size_t i = (size_t)M * Npad; i < hx.size(); ++i) if (hx[i] != 0.f) { ++bad; } }
   printf("fp8 epi %d  M=%d N=%d K=%d: %zu of %zu checked elements outside tolerance%s  (max rel err %.3g)\n", epi, M, N, K, bad, checked, bad ? "  <-- FAIL" : " (ok)", maxrel);
   for (int i = 0; i < 3; ++i) run();
   CK(hipStreamSynchronize(s));
@@ -136,7 +141,7 @@ static int run_fp8(int M, int N, int K, int epi, int iters, int tokens) {
 
 int main(int argc, char** argv) {
   { hipDeviceProp_t pr; CK(hipGetDeviceProperties(&pr, 0)); nCU = pr.multiProcessorCount; }
-  if (argc > 4 && atoi(argv[4]) >= 30 && atoi(argv[4]) <= 33)
+  if (argc > 4 && ((atoi(argv[4]) >= 30 && atoi(argv[4]) <= 33) || atoi(argv[4]) == 37))
     return run_fp8(atoi(argv[1]), atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argc > 5 ? atoi(argv[5]) : 20, argc > 6 ? atoi(argv[6]) : 197);
   int M = argc > 1 ? atoi(argv[1]) : 12608, N = argc > 2 ? atoi(argv[2]) : 3072, K = argc > 3 ? atoi(argv[3]) : 768;
   int epi = argc > 4 ? atoi(argv[4]) : 2, iters = argc > 5 ? atoi(argv[5]) : 20, tokens = argc > 6 ? atoi(argv[6]) : 197;
@@ -149,11 +154,13 @@ int main(int argc, char** argv) {
   CK(hipMalloc(&A, hA.size() * 2)); CK(hipMalloc(&W, hW.size() * 2)); CK(hipMalloc(&out, (size_t)M * Npad * 2));
   CK(hipMalloc(&bias, Npad * 4)); CK(hipMalloc(&x, (size_t)(M + M / 196 + 2) * Npad * 4)); CK(hipMalloc(&slab, (size_t)((M + 127) / 128) * 2 * Npad * 4));
   CK(hipMalloc(&pos, (size_t)200 * Npad * 4));
+  float* ls; CK(hipMalloc(&ls, Npad * 4));      // the LayerScale of epi 7 / 17: distinct per column, some negative
+  { std::vector<float> hg(Npad, 0.f); for (int n = 0; n < N; ++n) hg[n] = (n % 5 == 3 ? -1.f : 1.f) * (0.25f + (n % 17) / 16.f); CK(hipMemcpy(ls, hg.data(), Npad * 4, hipMemcpyHostToDevice)); }
   CK(hipMemcpy(A, hA.data(), hA.size() * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(W, hW.data(), hW.size() * 2, hipMemcpyHostToDevice));
   CK(hipMemset(bias, 0, Npad * 4)); CK(hipMemset(x, 0, (size_t)(M + M / 196 + 2) * Npad * 4)); CK(hipMemset(pos, 0, (size_t)200 * Npad * 4));
   GemmArgs g{};
   g.A = A; g.lda = K; g.W = W; g.ldw = K; g.bias = bias; g.M = M; g.N = N; g.K = K;
-  g.tiles_m = (M + 127) / 128; g.tiles_n = Npad / 128; g.out = out; g.ldo = Npad; g.x = x; g.ldx = Npad;
+  g.tiles_m = (M + 127) / 128; g.tiles_n = Npad / 128; g.out = out; g.ldo = Npad; g.x = x; g.ldx = Npad; g.ls = ls;
   g.score_site = (epi == 2 || epi == 13) ? 1 : ((epi == 5 || epi == 14) ? 2 : 0); g.tokens = tokens; g.slab = slab; g.slab_ld = Npad; g.pos = pos; g.patches = 196; g.prefix = 1; g.group_m = argc > 7 ? atoi(argv[7]) : 0;
 #ifdef GEMM_STAMPS
   unsigned long long* stamps; CK(hipMalloc(&stamps, (size_t)g.tiles_m * g.tiles_n * 64 * 8)); CK(hipMemset(stamps, 0, (size_t)g.tiles_m * g.tiles_n * 64 * 8));
@@ -174,20 +181,22 @@ int main(int argc, char** argv) {
     switch (epi) { case 15: if (N == 768) launch256ln<3>(g, s); else if (N == 1024) launch256ln<4>(g, s); else launch256ln<5>(g, s); break;
                    case 0: launch<EPI_BF16>(g, s); break; case 1: launch<EPI_RESID>(g, s); break; case 2: launch<EPI_FC1, 1>(g, s); break; case 5: launch<EPI_FC1, 2>(g, s); break; case 6: launch<EPI_FC1, 0>(g, s); break;
                    case 3: launch<EPI_PATCH>(g, s); break; case 4: launch<EPI_F32>(g, s); break;
+                   case 7: launch<EPI_RESID_LS>(g, s); break; case 17: launch256<EPI_RESID_LS>(g, s); break;
                    case 10: launch256<EPI_BF16>(g, s); break; case 11: launch256<EPI_RESID>(g, s); break;
                    case 12: launch256<EPI_FC1>(g, s); break; case 13: launch256<EPI_FC1, 1>(g, s); break; case 14: launch256<EPI_FC1, 2>(g, s); break;
                    case 40: launch256w4<EPI_BF16>(g, s); break; case 41: launch256w4<EPI_RESID>(g, s); break; case 42: launch256w4<EPI_FC1>(g, s); break;
                    default: break; }
   };
   if (epi >= 10) {   // verify the large-tile kernel against the (oracle-validated) 128x128 kernel, bit for bit
-    const bool resid = (epi % 10) == 1 || epi == 15, fc1 = (epi % 10) == 2, sc1 = epi == 13, sc2 = epi == 14;
+    const bool ls_form = epi == 17;
+    const bool resid = (epi % 10) == 1 || epi == 15 || ls_form, fc1 = (epi % 10) == 2, sc1 = epi == 13, sc2 = epi == 14;
     const size_t se = (size_t)((M + 127) / 128) * 2 * Npad;
     std::vector<float> slab_ref(se);
     size_t xe = (size_t)(M + M / 196 + 2) * Npad, oe = (size_t)M * Npad;
     CK(hipMemset(x, 0, xe * 4)); CK(hipMemset(out, 0, oe * 2));
     GemmArgs r = g; r.tiles_m = (M + 127) / 128; r.tiles_n = Npad / 128;
     if (sc1 || sc2) CK(hipMemset(slab, 0, se * 4));
-    if (resid) launch<EPI_RESID>(r, s); else if (fc1) launch<EPI_FC1, 0>(r, s); else if (sc1) launch<EPI_FC1, 1>(r, s); else if (sc2) launch<EPI_FC1, 2>(r, s); else launch<EPI_BF16>(r, s);
+    if (ls_form) launch<EPI_RESID_LS>(r, s); else if (resid) launch<EPI_RESID>(r, s); else if (fc1) launch<EPI_FC1, 0>(r, s); else if (sc1) launch<EPI_FC1, 1>(r, s); else if (sc2) launch<EPI_FC1, 2>(r, s); else launch<EPI_BF16>(r, s);
     CK(hipStreamSynchronize(s));
     if (sc1 || sc2) { CK(hipMemcpy(slab_ref.data(), slab, se * 4, hipMemcpyDeviceToHost)); CK(hipMemset(slab, 0, se * 4)); }
     std::vector<float> xr(resid ? xe : 0); std::vector<uint16_t> orf(resid ? 0 : oe);
@@ -300,7 +309,7 @@ int main(int argc, char** argv) {
   }
   if (const char* st = getenv("GEMM_STRESS")) {   // race screen: many launches, every result compared with the first
     const int reps = atoi(st);
-    const bool resid = (epi % 10) == 1;
+    const bool resid = (epi % 10) == 1 || epi == 17;
     size_t xe = (size_t)(M + M / 196 + 2) * Npad, oe = (size_t)M * Npad, se = (size_t)((M + 127) / 128) * 2 * Npad;
     std::vector<float> x0(resid ? xe : 0), xi(resid ? xe : 0), s0(se), si(se); std::vector<uint16_t> o0(resid ? 0 : oe), oi(resid ? 0 : oe);
     int bad_runs = 0;

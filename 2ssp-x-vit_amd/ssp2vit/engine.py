@@ -38,7 +38,10 @@ class VitEngine:
         0 = resident attention kernels only (d_h = 64 up to 288 tokens); 1 = longer d_h = 64 sequences (384-pixel /16: 577 tokens,
         224-pixel /8: 785) on the key-streaming kernel; 2 = every d_h = 64 attention streams (cross-checks).  A twin inherits it.
         Token layout: `weights["prefix_tokens"]` (default 1; 2 = CLS + distillation token, DeiT) and a distillation head when the
-        dictionary has `head_dist_w` (logits = mean of the CLS and DIST heads) go to ssp2_create_ext; a twin inherits them too."""
+        dictionary has `head_dist_w` (logits = mean of the CLS and DIST heads) go to ssp2_create_ext; a twin inherits them too.
+        LayerScale: `weights["ls1.i"]` / `weights["ls2.i"]` (fp32 [dim]: timm Block.ls1 / ls2 gamma) scale block i's attention / MLP
+        branch before the residual add (ssp2_set_layer_scale); a block without the key runs the plain residual epilogue.  The lab
+        build's options ln_fusion / defer_resid are not extended to such a branch: it takes the product kernel form."""
         if precision not in ("bf16", "fp8"):
             raise ValueError(f"precision must be 'bf16' or 'fp8', got {precision!r}")
         if attn_stream is not None and (isinstance(attn_stream, bool) or attn_stream not in (0, 1, 2)):
@@ -48,7 +51,7 @@ class VitEngine:
             src = _twin_of
             attn_stream = src.attn_stream
             weights = dict(depth=src.depth, dim=src.dim, classes=src.classes, img=src.img, patch=src.patch, heads=src.heads,
-                           eps=src.eps, prefix_tokens=src.prefix_tokens, dist_head=src.dist_head,
+                           eps=src.eps, prefix_tokens=src.prefix_tokens, dist_head=src.dist_head, _layer_scale=src.layer_scale,
                            **{f"fc1_w.{i}": torch.empty(int(d), 0) for i, d in enumerate(_d_int)})
             device = src.device
         if not torch.cuda.is_available():
@@ -68,6 +71,7 @@ class VitEngine:
         self.prefix_tokens = int(weights.get("prefix_tokens", 1))
         self.dist_head = int(weights.get("dist_head", "head_dist_w" in weights))
         self.d_int = [int(weights[f"fc1_w.{i}"].shape[0]) for i in range(self.depth)]
+        self.layer_scale = self._layer_scale_of(weights, self.depth, self.dim)      # per block: (ls1 present, ls2 present)
         self.score_ld = max((d + 63) // 64 * 64 for d in self.d_int)
         self.max_images = int(max_images)
         self.absent = [bool(weights.get(f"attn_absent.{i}", False)) for i in range(self.depth)]
@@ -98,6 +102,17 @@ class VitEngine:
                 self.absent = list(_twin_of.absent)
 
     # ------------------------------------------------------------------ weights
+    @staticmethod
+    def _layer_scale_of(w: Dict, depth: int, dim: int) -> Tuple[Tuple[bool, bool], ...]:
+        """Which residual branches of `w` carry a LayerScale (`ls1.i` / `ls2.i`); a gamma that is not [dim] is refused by name."""
+        if "_layer_scale" in w:
+            return tuple(w["_layer_scale"])
+        for i in range(depth):
+            for k in (f"ls1.{i}", f"ls2.{i}"):
+                if k in w and int(w[k].numel()) != dim:
+                    raise ValueError(f"{k}: a LayerScale gamma of {int(w[k].numel())} values on a hidden size of {dim}")
+        return tuple((f"ls1.{i}" in w, f"ls2.{i}" in w) for i in range(depth))
+
     def _load(self, w: Dict) -> None:
         """fp32 tensors in nn.Linear layout -> the engine's bf16 / padded weight image.  The rounding and the padding run
         in a kernel; a tensor that already lives on this GPU (a module moved to the device, as the reference keeps it)
@@ -134,12 +149,22 @@ class VitEngine:
             ptrs = (C.c_void_p * m)(*[b[2].data_ptr() for b in batch])
             numels = (C.c_size_t * m)(*[b[2].numel() for b in batch])
             self._check(self.lib.ssp2_load_tensors_dev(self.h, m, kinds, layers, ptrs, numels))
+        # LayerScale: fp32 as it is, one small copy per branch (no tensor kind of the batched ingest: the kinds' order is pinned)
+        for i, has in enumerate(self.layer_scale):
+            for br in (0, 1):
+                if has[br]:
+                    t = w[f"ls{br + 1}.{i}"].detach()
+                    on_dev = t.device == self.device
+                    t = (t if on_dev else t.to("cpu")).to(torch.float32).contiguous().view(-1)
+                    keep.append(t)
+                    self._check(self.lib.ssp2_set_layer_scale(self.h, i, br, _ptr(t), int(on_dev)))
+        if keep:
             torch.cuda.current_stream(self.device).synchronize()
 
     def geometry_key(self):
         """What two engines must share for one to take over the other's handle (workspace, weight storage): see `reload`."""
         return (str(self.device), self.precision, self.lib_variant, self.img, self.patch, self.dim, self.heads, self.depth, self.classes,
-                float(self.eps), tuple(int(d) for d in self.d_int), self.prefix_tokens, self.dist_head)
+                float(self.eps), tuple(int(d) for d in self.d_int), self.prefix_tokens, self.dist_head, self.layer_scale)
 
     def reload(self, weights: Dict) -> "VitEngine":
         """Another model of the SAME geometry into this engine: every tensor is ingested again (device-to-device rounding kernels), the
@@ -152,6 +177,8 @@ class VitEngine:
             raise Ssp2Error("reload: FFN widths differ")
         if (int(weights.get("prefix_tokens", 1)), int(weights.get("dist_head", "head_dist_w" in weights))) != (self.prefix_tokens, self.dist_head):
             raise Ssp2Error("reload: token layouts differ (prefix tokens / distillation head)")
+        if self._layer_scale_of(weights, self.depth, self.dim) != self.layer_scale:
+            raise Ssp2Error("reload: LayerScale differs (which residual branches carry a gamma)")
         with torch.cuda.device(self.device):
             self._load(weights)
             for l in range(self.depth):
@@ -418,11 +445,18 @@ class VitEngine:
         return out
 
     def linear(self, a: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], epilogue: str = "bf16",
-               x: Optional[torch.Tensor] = None, kernel: str = "auto") -> torch.Tensor:
+               x: Optional[torch.Tensor] = None, kernel: str = "auto", *, gamma: Optional[torch.Tensor] = None,
+               xin: Optional[torch.Tensor] = None, rev: int = 0) -> torch.Tensor:
         """One projection of the forward on its own (ssp2_linear_bf16): a bf16 [M, K], weight [N, K] (any float dtype,
         rounded to bf16 like autocast does), bias [N] or None.  epilogue "bf16" / "gelu" -> bf16 [M, N];
-        "resid" -> x (f32 [M, N]) updated in place and returned."""
+        "resid" -> x (f32 [M, N]) updated in place and returned.
+        gamma (f32 [N], "resid" only): the branch's LayerScale — x = xin + fl32(gamma * bf16(...)) (ssp2_linear_ls_bf16), xin (default
+        x) read at x's row stride, rev the walk direction of the 256 x 256 kernel's tiles."""
         epi = {"bf16": 0, "resid": 1, "gelu": 2}[epilogue]
+        if gamma is None and (xin is not None or rev):
+            raise ValueError("xin / rev belong to the LayerScale form (gamma=...)")
+        if gamma is not None and epi != 1:
+            raise ValueError("gamma: LayerScale goes with the resid epilogue only")
         M, K = a.shape
         N = weight.shape[0]
         npad = (N + 255) // 256 * 256
@@ -433,12 +467,33 @@ class VitEngine:
             bp[:N].copy_(bias.to(self.device, torch.bfloat16).float())
         a = a.to(self.device, torch.bfloat16).contiguous()
         out = None if epi == 1 else torch.empty(M, N, dtype=torch.bfloat16, device=self.device)
+        if gamma is not None:
+            # the LayerScale form takes x (and xin, at the same row stride) as row-major f32 [>= M, >= N]: ldx = x's row stride
+            for name, t in (("x", x), ("xin", xin)):
+                if (t is None and name == "x") or (t is not None and (t.device.type != "cuda" or t.dtype != torch.float32 or t.dim() != 2
+                                                                      or t.stride(1) != 1 or t.shape[0] < M or t.shape[1] < N)):
+                    raise ValueError(f"the LayerScale form needs {name} as a row-major f32 device tensor of >= [{M}, {N}]")
+            if xin is not None and xin.stride(0) != x.stride(0):
+                raise ValueError("xin must have x's row stride (the kernel reads both at ldx)")
+            gp = self._gamma_vec(gamma, N)
+            self._check(self.lib.ssp2_linear_ls_bf16(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), _ptr(a), K, _ptr(wp), K,
+                                                     _ptr(bp), _ptr(gp), M, N, K, _ptr(x), _ptr(xin), x.stride(0),
+                                                     {"auto": 0, "small": 1, "big": 2}[kernel], int(rev)))
+            return x
         if epi == 1 and (x is None or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[1] != N or x.shape[0] < M):
             raise ValueError("resid epilogue needs a contiguous f32 x [>= M, N]")
         self._check(self.lib.ssp2_linear_bf16(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), epi, _ptr(a), K,
                                         _ptr(wp), K, _ptr(bp), M, N, K, _ptr(out), N, _ptr(x if epi == 1 else None), N,
                                         {"auto": 0, "small": 1, "big": 2}[kernel]))
         return x if epi == 1 else out
+
+    def _gamma_vec(self, gamma: torch.Tensor, N: int) -> torch.Tensor:
+        """A LayerScale operand of the operator entries: fp32 [N] on the device, padded to 256 like a bias, values untouched."""
+        if gamma.numel() != N:
+            raise ValueError(f"gamma: {gamma.numel()} values for {N} output columns")
+        gp = torch.zeros((N + 255) // 256 * 256, dtype=torch.float32, device=self.device)
+        gp[:N].copy_(gamma.detach().reshape(-1).to(self.device, torch.float32))
+        return gp
 
     def quantise_e4m3(self, w: torch.Tensor, *, rows_pad: Optional[int] = None, ld8: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The fp8 mode's weight quantiser on its own (ssp2_quantise_rows_e4m3, what ssp2_set_precision runs): w [rows, cols] (any float
@@ -458,15 +513,18 @@ class VitEngine:
                     rows: Optional[int] = None, ascale: Optional[torch.Tensor] = None, ascale_const: float = 0.0,
                     out: Optional[torch.Tensor] = None, x: Optional[torch.Tensor] = None, xin: Optional[torch.Tensor] = None,
                     score_site: int = 0, tokens: int = 0, group: int = 0, n_img: int = 0, slab_ld: Optional[int] = None,
-                    rev: int = 0):
+                    rev: int = 0, gamma: Optional[torch.Tensor] = None):
         """One fp8 projection of the forward on its own (ssp2_linear_e4m3): a8 uint8 e4m3 [>= rows, lda] (rows = a8.shape[0] by default,
         lda = its row stride), w8 uint8 [N, K] e4m3 with K the contraction length (K % 128 == 0), wscale f32 [N], bias [N] or None (rounded
         to bf16); W, wscale and bias are padded to 256 rows like `linear` does.  Activation scale per row from ascale (f32 [>= rows]),
         or ascale_const, or 1.  epilogue "bf16" -> out bf16 [rows, >= N]; "resid" -> x (f32 [>= rows, ld]) = xin (default x) +
         bf16(...), returned; "gelu" -> out uint8 [rows, >= N] e4m3 bytes, and with score_site 1 / 2 (tokens, group, n_img: the row
         layout of ssp2_rows) the tuple (out, slab f32 [2 * ceil(rows / 256), 2, slab_ld]), slab_ld defaulting to N: entry t
-        covers rows 128 t .. 128 t + 127 (zeros past the last row).  rev: the walk direction of the tiles (the forward alternates them)."""
+        covers rows 128 t .. 128 t + 127 (zeros past the last row).  rev: the walk direction of the tiles (the forward alternates them).
+        gamma (f32 [N], "resid" only): the branch's LayerScale, x = xin + fl32(gamma * bf16(...)) (ssp2_linear_ls_e4m3)."""
         epi = {"bf16": 0, "resid": 1, "gelu": 2}[epilogue]
+        if gamma is not None and epi != 1:
+            raise ValueError("gamma: LayerScale goes with the resid epilogue only")
         N, K = w8.shape
         M = a8.shape[0] if rows is None else int(rows)
         for name, t in (("a8", a8), ("w8", w8), ("out", out if epi == 2 else None)):
@@ -507,6 +565,12 @@ class VitEngine:
             if score_site:
                 slab_ld = N if slab_ld is None else int(slab_ld)
                 slab = torch.full((2 * ((M + 255) // 256), 2, slab_ld), float("nan"), dtype=torch.float32, device=self.device)
+        if gamma is not None:
+            gp = self._gamma_vec(gamma, N)
+            self._check(self.lib.ssp2_linear_ls_e4m3(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), _ptr(a8), a8.stride(0),
+                                                     _ptr(ascale), float(ascale_const), _ptr(wp), K, _ptr(sp), _ptr(bp), _ptr(gp), M, N, K,
+                                                     _ptr(x), _ptr(xin), ldx, int(rev)))
+            return x
         self._check(self.lib.ssp2_linear_e4m3(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), epi, _ptr(a8), a8.stride(0),
                                               _ptr(ascale), float(ascale_const), _ptr(wp), K, _ptr(sp), _ptr(bp), M, N, K,
                                               _ptr(out) if epi != 1 else None, ldo, _ptr(x) if epi == 1 else None,

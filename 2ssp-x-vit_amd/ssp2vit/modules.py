@@ -31,13 +31,26 @@ class _EngineMlp(nn.Module):
         self.fc2 = nn.Linear(inter, dim)
 
 
+class _EngineLayerScale(nn.Module):
+    """timm's LayerScale as a parameter container: `.gamma` [dim], out of place (`inplace = False`)."""
+    inplace = False
+
+    def __init__(self, dim):
+        super().__init__()
+        self.gamma = nn.Parameter(torch.ones(dim))
+
+
 class _EngineBlock(nn.Module):
-    def __init__(self, dim, heads, inter, eps):
+    def __init__(self, dim, heads, inter, eps, ls1=False, ls2=False):
         super().__init__()
         self.norm1 = nn.LayerNorm(dim, eps=eps)
         self.attn = _EngineAttn(dim, heads)
+        if ls1:
+            self.ls1 = _EngineLayerScale(dim)
         self.norm2 = nn.LayerNorm(dim, eps=eps)
         self.mlp = _EngineMlp(dim, inter)
+        if ls2:
+            self.ls2 = _EngineLayerScale(dim)
 
 
 class _PatchEmbed(nn.Module):
@@ -48,7 +61,8 @@ class _PatchEmbed(nn.Module):
 
 class EngineViT(nn.Module):
     """timm-layout container (`.blocks[i].{norm1,attn.qkv,attn.proj,norm2,mlp.fc1,mlp.fc2}`, `.patch_embed.proj`,
-    `.cls_token`, `.pos_embed`, `.norm`, `.head`; distilled DeiT weights add timm's `.dist_token` and `.head_dist`); `model(px)`
+    `.cls_token`, `.pos_embed`, `.norm`, `.head`; distilled DeiT weights add timm's `.dist_token` and `.head_dist`, LayerScale weights
+    `.blocks[i].ls1.gamma` / `.ls2.gamma`); `model(px)`
     returns logits computed by libssp2vit."""
 
     def __init__(self, w: Dict):
@@ -60,7 +74,8 @@ class EngineViT(nn.Module):
         self.pos_embed = nn.Parameter(torch.zeros(1, w["pos"].shape[1], dim))
         if int(w.get("prefix_tokens", 1)) == 2:
             self.dist_token = nn.Parameter(torch.zeros(1, 1, dim))
-        self.blocks = nn.ModuleList([_EngineBlock(dim, heads, int(w[f"fc1_w.{i}"].shape[0]), eps) for i in range(depth)])
+        self.blocks = nn.ModuleList([_EngineBlock(dim, heads, int(w[f"fc1_w.{i}"].shape[0]), eps, f"ls1.{i}" in w, f"ls2.{i}" in w)
+                                     for i in range(depth)])
         self.norm = nn.LayerNorm(dim, eps=eps)
         self.head = nn.Linear(dim, int(w["classes"]))
         if "head_dist_w" in w:
@@ -79,6 +94,9 @@ class EngineViT(nn.Module):
                 put(b.norm2.weight, w[f"ln2_g.{i}"]); put(b.norm2.bias, w[f"ln2_b.{i}"])
                 put(b.mlp.fc1.weight, w[f"fc1_w.{i}"]); put(b.mlp.fc1.bias, w[f"fc1_b.{i}"])
                 put(b.mlp.fc2.weight, w[f"fc2_w.{i}"]); put(b.mlp.fc2.bias, w[f"fc2_b.{i}"])
+                for name in ("ls1", "ls2"):
+                    if f"{name}.{i}" in w:
+                        put(getattr(b, name).gamma, w[f"{name}.{i}"])
             put(self.norm.weight, w["lnf_g"]); put(self.norm.bias, w["lnf_b"])
             put(self.head.weight, w["head_w"]); put(self.head.bias, w["head_b"])
             if hasattr(self, "dist_token"):

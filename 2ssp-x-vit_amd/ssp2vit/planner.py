@@ -101,11 +101,14 @@ def plan_from_stats(st: ModelStats, target_sparsity: float, min_remaining: int =
     return TwoSSPPlan(target_sparsity, B, best.k, best.t, (best.k / B) if B > 0 else 0.0, best.removed, int(best.err))
 
 
-def stats_from_shapes(dim: int, depth: int, inter: Sequence[int] | int, classes: int, tokens: int, patch: int) -> ModelStats:
-    """Parameter counts of a standard ViT (fused or split qkv count the same)."""
+def stats_from_shapes(dim: int, depth: int, inter: Sequence[int] | int, classes: int, tokens: int, patch: int,
+                      layer_scale: int = 0) -> ModelStats:
+    """Parameter counts of a standard ViT (fused or split qkv count the same).  `layer_scale`: LayerScale vectors per block (2 for
+    timm's ls1 + ls2): they count in the total, as in the reference's model.parameters(), and in neither the attention nor the FFN
+    count (the reference reads those from the attn / mlp sub-modules)."""
     inters = list(inter) if not isinstance(inter, int) else [inter] * depth
     attn = [4 * dim * dim + 4 * dim] * depth
     ffn = [d * dim + d + dim * d + dim for d in inters]
-    blocks = sum(a + f + 4 * dim for a, f in zip(attn, ffn))
+    blocks = sum(a + f + 4 * dim + layer_scale * dim for a, f in zip(attn, ffn))
     total = blocks + (3 * patch * patch * dim + dim) + dim + tokens * dim + 2 * dim + (classes * dim + classes)
     return ModelStats(total, dim, inters, attn, ffn)

@@ -144,7 +144,7 @@ def engine_for(model, device="cuda", max_images: int = 64, precision: Optional[s
     precision = precision or DEFAULT_PRECISION
     attn_stream = attn_stream_setting(attn_stream)
     key = id(model)
-    fp = _fingerprint(model) + (precision, attn_stream) + _weights.token_layout(model)
+    fp = _fingerprint(model) + (precision, attn_stream) + _weights.token_layout(model) + (_weights.has_layer_scale(model),)
     hit = _ENGINES.get(key)
     if hit is not None and hit[0] == fp and hit[1].max_images >= max_images:
         return hit[1]
@@ -196,6 +196,7 @@ def _from_pool(flat, dev, max_images: int, precision: str, attn_stream: int = 0)
             same = (str(e.device) == str(dev) and e.precision == precision and e.max_images >= max_images and e.lib_variant is None
                     and getattr(e, "attn_stream", 0) == attn_stream
                     and (e.prefix_tokens, e.dist_head) == (int(flat.get("prefix_tokens", 1)), int("head_dist_w" in flat))
+                    and tuple(e.layer_scale) == tuple((f"ls1.{l}" in flat, f"ls2.{l}" in flat) for l in range(e.depth))
                     and (e.img, e.patch, e.dim, e.heads, e.depth, e.classes) == tuple(int(flat[k]) for k in ("img", "patch", "dim", "heads", "depth", "classes"))
                     and abs(e.eps - float(flat.get("eps", 1e-6))) < 1e-15
                     and [int(d) for d in e.d_int] == [int(flat[f"fc1_w.{l}"].shape[0]) for l in range(e.depth)])

@@ -15,6 +15,8 @@ Keys (all tensors fp32, CPU, contiguous; layer index ``i`` in ``0..depth-1``)::
     prefix_tokens                                    1 (CLS), or 2 (CLS + distillation token: distilled DeiT); default 1
     dist [1,1,dim]                                   the distillation token (prefix_tokens == 2)
     head_dist_w [classes,dim]  head_dist_b [classes] the distillation head: logits = (head(CLS) + head_dist(DIST)) / 2
+    ls1.i ls2.i [dim]                                LayerScale (timm Block.ls1 / ls2 gamma; absent = none): x += ls1 * attn(...),
+                                                     x += ls2 * mlp(...); kept fp32, never rounded
 
 N = patches + prefix_tokens: pos covers every token.  A model with two prefix tokens and no ``head_dist_w`` (HF
 ``DeiTForImageClassification``) reads its head on CLS only.
@@ -27,7 +29,7 @@ transformers>=5.
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -72,9 +74,24 @@ VIT_CONFIGS = {
     "deit_small_distilled_patch16_224_d2": (224, 16, 384, 6, 1536, 2),
     "deit_base_distilled_patch16_384_d2": (384, 16, 768, 12, 3072, 2),
     "deit_test_distilled_patch16_32": (32, 16, 64, 4, 128, 4),
+    # LayerScale on both residual branches (LAYER_SCALE below): the DINOv2 backbones with a linear head at 518 pixels (1370 tokens, d_h 64:
+    # the key-streaming attention) and at 224 (257 tokens), and test cuts
+    "vit_small_patch14_dinov2": (518, 14, 384, 6, 1536, 12),
+    "vit_base_patch14_dinov2": (518, 14, 768, 12, 3072, 12),
+    "vit_large_patch14_dinov2": (518, 14, 1024, 16, 4096, 24),
+    "vit_small_patch14_dinov2_224": (224, 14, 384, 6, 1536, 12),
+    "vit_base_patch14_dinov2_224": (224, 14, 768, 12, 3072, 12),
+    "vit_large_patch14_dinov2_224": (224, 14, 1024, 16, 4096, 24),
+    "vit_small_patch14_dinov2_d2": (518, 14, 384, 6, 1536, 2),
+    "vit_small_patch16_224_ls_d2": (224, 16, 384, 6, 1536, 2),
+    "vit_test_patch16_32_ls": (32, 16, 64, 4, 128, 4),
 }
 # VIT_CONFIGS entries with a distillation token and head (their entries stay (img, patch, dim, heads, d_int, depth))
 DISTILLED = frozenset(k for k in VIT_CONFIGS if k.startswith("deit_") and "_distilled_" in k)
+
+
+# VIT_CONFIGS entries whose blocks carry LayerScale (synthetic_weights draws ls1 / ls2 for them by default)
+LAYER_SCALE = frozenset(k for k in VIT_CONFIGS if "_dinov2" in k or k.endswith(("_ls", "_ls_d2")))
 
 
 def prefix_tokens_of(name: str) -> int:
@@ -88,12 +105,14 @@ def n_tokens(w: Dict) -> int:
 
 def synthetic_weights(name: str = "vit_base_patch16_224", classes: int = 1000, seed: int = 0,
                       std: float = 0.02, eps: float = 1e-6, spread: Optional[float] = None,
-                      bias_std: float = 0.0) -> Dict:
+                      bias_std: float = 0.0, layer_scale: Optional[bool] = None) -> Dict:
     """Seeded random-init weights of a named architecture (no checkpoints exist offline).
 
     trunc-normal(std) matrices, LN gamma=1 beta=0, zero (or N(0,bias_std)) biases.  ``spread`` scales
     fc1 rows by a log-uniform factor in [1/spread, spread] so stage-1 scores are well separated
-    (SURVEY.md §8d).
+    (SURVEY.md §8d).  ``layer_scale`` (default: the model is in LAYER_SCALE) adds ``ls1.i`` / ``ls2.i``: magnitudes log-uniform in
+    [1e-3, 2], about a quarter of them negative — not the 1e-5 init value, so that a column-mapping error moves a result by far more
+    than any tolerance.  They are drawn from a generator of their own: the other tensors are the same with and without them.
     """
     img, patch, dim, heads, inter, depth = VIT_CONFIGS[name]
     g = torch.Generator().manual_seed(seed)
@@ -131,6 +150,13 @@ def synthetic_weights(name: str = "vit_base_patch16_224", classes: int = 1000, s
     if prefix == 2:
         w["dist"] = tn(1, 1, dim)
         w["head_dist_w"] = tn(classes, dim); w["head_dist_b"] = bias(classes)
+    if (name in LAYER_SCALE) if layer_scale is None else layer_scale:
+        gl = torch.Generator().manual_seed(seed + 7919)
+        lo, hi = math.log(1e-3), math.log(2.0)
+        for i in range(depth):
+            for k in ("ls1", "ls2"):
+                mag = torch.exp(torch.rand(dim, generator=gl) * (hi - lo) + lo)
+                w[f"{k}.{i}"] = torch.where(torch.rand(dim, generator=gl) < 0.25, -mag, mag)
     return w
 
 
@@ -187,6 +213,42 @@ def _check_timm_token_layout(model) -> int:
     if npt is not None and int(npt) != prefix:
         raise ValueError(f"num_prefix_tokens={int(npt)}: the engine supports CLS or CLS + dist_token (1 or 2 prefix tokens)")
     return prefix
+
+
+def _timm_layer_scale(block, name: str, dim: int, where: str) -> Optional[torch.Tensor]:
+    """gamma of a timm block's `ls1` / `ls2` (LayerScale: x * gamma, an fp32 product under autocast); None for an absent attribute or an
+    nn.Identity (init_values=None).  Refused by name: `inplace=True` (x.mul_(gamma) rounds the product to the branch's bf16 — other
+    arithmetic), HF's `lambda1` parameter, anything else without a gamma, a gamma that is not [dim]."""
+    ls = getattr(block, name, None)
+    if ls is None or isinstance(ls, torch.nn.Identity):
+        return None
+    if getattr(ls, "lambda1", None) is not None:
+        raise ValueError(f"{where}.{name}.lambda1: HF-style LayerScale (Dinov2LayerScale) is not supported")
+    gamma = getattr(ls, "gamma", None)
+    if gamma is None:
+        raise ValueError(f"{where}.{name}: a {type(ls).__name__} without a `gamma` parameter is not a LayerScale this build knows")
+    if bool(getattr(ls, "inplace", False)):
+        raise ValueError(f"{where}.{name}.inplace: an in-place LayerScale rounds gamma * x to bf16 under autocast (other arithmetic); not supported")
+    if gamma.dim() != 1 or int(gamma.numel()) != dim:
+        raise ValueError(f"{where}.{name}.gamma: shape {tuple(gamma.shape)} is not [{dim}]")
+    return _f32(gamma)
+
+
+def _refuse_hf_layer_scale(layer, where: str) -> None:
+    """HF DINOv2 blocks (`layer_scale1.lambda1` / `layer_scale2.lambda1`): its classifier concatenates CLS with the mean patch token, which
+    the engine's head does not compute — refused by name rather than pruned as another network."""
+    for name in ("layer_scale1", "layer_scale2"):
+        if getattr(layer, name, None) is not None:
+            raise ValueError(f"{where}.{name}.lambda1: HF DINOv2 LayerScale is not supported (its head reads CLS and the mean patch token); "
+                             "use the timm layout (blocks[i].ls1.gamma)")
+
+
+def has_layer_scale(model) -> Tuple[Tuple[bool, bool], ...]:
+    """Per block of a timm-layout module: (ls1 is a LayerScale, ls2 is one), read without copying a weight; () for the HF layouts."""
+    if detect_layout(model) != "timm":
+        return ()
+    is_ls = lambda b, n: getattr(b, n, None) is not None and not isinstance(getattr(b, n), torch.nn.Identity)
+    return tuple((is_ls(b, "ls1"), is_ls(b, "ls2")) for b in model.blocks)
 
 
 def _hf_base(model):
@@ -269,6 +331,10 @@ def from_module(model) -> Dict:
             w[f"ln2_g.{i}"], w[f"ln2_b.{i}"] = _f32(b.norm2.weight), _f32(b.norm2.bias)
             w[f"fc1_w.{i}"], w[f"fc1_b.{i}"] = _f32(b.mlp.fc1.weight), _f32(b.mlp.fc1.bias)
             w[f"fc2_w.{i}"], w[f"fc2_b.{i}"] = _f32(b.mlp.fc2.weight), _f32(b.mlp.fc2.bias)
+            for name in ("ls1", "ls2"):
+                gamma = _timm_layer_scale(b, name, int(b.norm1.weight.shape[0]), f"blocks[{i}]")
+                if gamma is not None:
+                    w[f"{name}.{i}"] = gamma
         w["lnf_g"], w["lnf_b"] = _f32(model.norm.weight), _f32(model.norm.bias)
         w["head_w"], w["head_b"] = _f32(model.head.weight), _bias_or_zeros(model.head)
         eps = float(model.norm.eps)
@@ -286,6 +352,7 @@ def from_module(model) -> Dict:
         w["patch_w"], w["patch_b"] = _f32(pe.weight), _f32(pe.bias)
         _hf_embeddings(emb, w)
         for i, l in enumerate(layers):
+            _refuse_hf_layer_scale(l, f"encoder.layer[{i}]")
             w[f"ln1_g.{i}"], w[f"ln1_b.{i}"] = _f32(l.layernorm_before.weight), _f32(l.layernorm_before.bias)
             att = getattr(l, "attention", None)
             sa = getattr(att, "attention", None)
@@ -310,6 +377,7 @@ def from_module(model) -> Dict:
         w["patch_w"], w["patch_b"] = _f32(pe.weight), _f32(pe.bias)
         _hf_embeddings(emb, w)
         for i, l in enumerate(layers):
+            _refuse_hf_layer_scale(l, f"layers[{i}]")
             w[f"ln1_g.{i}"], w[f"ln1_b.{i}"] = _f32(l.layernorm_before.weight), _f32(l.layernorm_before.bias)
             a = l.attention
             if hasattr(a, "q_proj"):
@@ -364,6 +432,10 @@ def from_state_dict(sd: Dict[str, torch.Tensor], config: Optional[Dict] = None, 
     opt = lambda k, n: f(k) if has(k) else torch.zeros(n)
     w: Dict = {}
     absent = set(int(i) for i in meta.get("attention_removed_blocks", []))
+    for k in sd:                                                         # HF DINOv2 LayerScale, under any prefix: refused by name (see from_module)
+        if k.endswith((".layer_scale1.lambda1", ".layer_scale2.lambda1")):
+            raise ValueError(f"{k}: HF DINOv2 LayerScale (layer_scale1.lambda1 / layer_scale2.lambda1) is not supported (its head reads CLS "
+                             "and the mean patch token); use the timm layout (blocks.N.ls1.gamma)")
     if has("patch_embed.proj.weight"):                                   # ---- timm
         layout = "timm"
         for k, what in (("reg_token", "register tokens"), ("fc_norm.weight", "a LayerNorm in front of the head (fc_norm: pooled head)")):
@@ -386,6 +458,12 @@ def from_state_dict(sd: Dict[str, torch.Tensor], config: Optional[Dict] = None, 
             w[f"ln2_g.{i}"], w[f"ln2_b.{i}"] = f(p + "norm2.weight"), f(p + "norm2.bias")
             w[f"fc1_w.{i}"], w[f"fc1_b.{i}"] = f(p + "mlp.fc1.weight"), f(p + "mlp.fc1.bias")
             w[f"fc2_w.{i}"], w[f"fc2_b.{i}"] = f(p + "mlp.fc2.weight"), f(p + "mlp.fc2.bias")
+            for name in ("ls1", "ls2"):                                  # LayerScale (a state dict cannot say `inplace`: that is a module attribute)
+                if has(p + name + ".gamma"):
+                    gamma = f(p + name + ".gamma")
+                    if gamma.dim() != 1 or int(gamma.numel()) != dim:
+                        raise ValueError(f"{p}{name}.gamma: shape {tuple(gamma.shape)} is not [{dim}]")
+                    w[f"{name}.{i}"] = gamma
             i += 1
         w["lnf_g"], w["lnf_b"] = f("norm.weight"), f("norm.bias")
         if not has("head.weight"):

@@ -158,6 +158,20 @@ int ssp2_load_tensor_dev(ssp2_handle h, int kind, int layer, const float* dev_pt
  * free to go when the call returns. */
 int ssp2_load_tensors_dev(ssp2_handle h, int count, const int* kinds, const int* layers, const float* const* dev_ptrs, const size_t* numels);
 
+/* Additive (ABI stays 7): LayerScale, the learned per-channel vector on a residual branch (timm Block.ls1 / ls2, `init_values`: every
+ * DINOv2 backbone, DeiT-III):  x = x + ls1.gamma * attn(norm1(x));  x = x + ls2.gamma * mlp(norm2(x)).
+ *   branch 0 = attention (ls1), 1 = MLP (ls2); gamma fp32 [dim], host memory or (on_device != 0) HBM.  It is held as fp32, never
+ *   rounded: under autocast the branch output is bf16 and gamma an fp32 parameter, so the epilogue computes
+ *   x_new = x_in + fl32(gamma[c] * float(bf16(acc + bias[c]))) — product and sum rounded separately, no fused multiply-add.
+ * A block and branch whose gamma was set runs the EPI_RESID_LS epilogue of both GEMM kernels, one that was not runs today's residual
+ * epilogue bit for bit.  The evaluation tail, ssp2_clone_weights (gamma is per hidden column: width pruning leaves it alone) and a
+ * dropped attention (x untouched) follow.  The lab-only forms (SSP2_OPT_LN_FUSION, SSP2_OPT_DEFER_RESID) are not extended: a branch
+ * with LayerScale takes the product form whatever those options say.  One small copy per call (dim floats) into storage reserved by
+ * ssp2_create (no allocation here); a host source
+ * synchronises the handle's stream, a device source is asynchronous on it.  A bad layer, a bad branch or a null pointer is SSP2_EINVAL
+ * before the device is touched. */
+int ssp2_set_layer_scale(ssp2_handle h, int layer, int branch /* 0 = attention, 1 = MLP */, const float* gamma, int on_device);
+
 /* Arithmetic of the three large projections (QKV, fc1, fc2) of launches with >= 4096 token rows.
  *   SSP2_PREC_BF16  (default) bf16 operands — the reference's CPU-autocast arithmetic, the parity mode.
  *   SSP2_PREC_FP8   opt-in, BASELINE.json configs[4]: OCP e4m3 operands on the CDNA4 scaled-MFMA path (2x the bf16 matrix
@@ -309,6 +323,18 @@ int ssp2_linear_e4m3(void* hip_stream, int epilogue, const uint8_t* a_dev, int l
                      const uint8_t* w_dev, int ldw, const float* wscale_dev, const float* bias_dev, int M, int N, int K,
                      void* out_dev, int ldo, float* x_dev, const float* xin_dev, int ldx,
                      int score_site, int tokens, int group, int n_img, float* slab_dev, int slab_ld, int rev);
+/* Additive (ABI stays 7): the residual projections WITH LayerScale on their own — ssp2_linear_bf16 / ssp2_linear_e4m3 with SSP2_EPI_RESID
+ * and one more operand, gamma_dev f32 [N], 16-byte aligned (read as it is, four columns at a time):
+ *   x_dev[M, ldx] = xin[M, ldx] + fl32(gamma[n] * float(bf16(pre)))   (xin_dev NULL: x_dev, in place)
+ * pre = acc + bias (bf16 operands) or fma(acc * ascale, wscale[n], bias[n]) (e4m3 operands); the product and the sum are two fp32
+ * roundings.  Operand layouts, `kernel` (0 forward's routing, 1 / 2 force the 128 x 128 / 256 x 256 kernel) and rev (walk direction
+ * of the 256 x 256 kernel's tiles, 0 / 1) as in those entries; rows past M and columns past N of x are not touched.  Every argument
+ * is checked before the device is touched. */
+int ssp2_linear_ls_bf16(void* hip_stream, const uint16_t* a_dev, int lda, const uint16_t* w_dev, int ldw, const float* bias_dev,
+                        const float* gamma_dev, int M, int N, int K, float* x_dev, const float* xin_dev, int ldx, int kernel, int rev);
+int ssp2_linear_ls_e4m3(void* hip_stream, const uint8_t* a_dev, int lda, const float* ascale_dev, float ascale_const,
+                        const uint8_t* w_dev, int ldw, const float* wscale_dev, const float* bias_dev, const float* gamma_dev,
+                        int M, int N, int K, float* x_dev, const float* xin_dev, int ldx, int rev);
 /* Additive (ABI stays 7): the fp8 mode's weight quantiser on its own (what ssp2_set_precision runs per weight): row r < rows of the bf16 w_dev
  * [rows, ld] gets scale_dev[r] = amax / 448 (1 for a zero row) and w8_dev[r, c] = e4m3(w * (1 / scale)), saturating, for c < cols;
  * columns [cols, ld8) and rows [rows, rows_pad) are zero bytes with scale 1.  ld8 >= cols, a multiple of 16. */
