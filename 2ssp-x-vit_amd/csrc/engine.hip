@@ -1726,6 +1726,45 @@ int ssp2_linear_bf16(void* hip_stream, int epilogue, const uint16_t* a_dev, int 
   return dispatch_gemm(&e, epilogue, false, g, -2);
 }
 
+// ... with everything the forward's bf16 launches set besides: the residual read from xin, fc1's pre-GELU copy (out2: the unfused hook's
+// operand, 128 x 128 kernel only) and its score sites, the walk direction.  The same dispatch_gemm(f8 = false) forms, no further one.
+// Every argument is checked before the device is touched.
+int ssp2_linear_bf16_ex(void* hip_stream, int epilogue, const uint16_t* a_dev, int lda, const uint16_t* w_dev, int ldw, const float* bias_dev,
+                        int M, int N, int K, uint16_t* out_dev, int ldo, uint16_t* out2_dev, float* x_dev, const float* xin_dev, int ldx,
+                        int score_site, int tokens, int group, int n_img, float* slab_dev, int slab_ld, int kernel, int rev) {
+  if (!a_dev || !w_dev || !bias_dev) return fail(SSP2_EINVAL, "linear_ex: null operand");
+  if (M <= 0 || N <= 0 || K <= 0 || (K % GEMM_BK) || (N % 64)) return fail(SSP2_EINVAL, "linear_ex: M=%d N=%d K=%d (K multiple of %d, N multiple of 64)", M, N, K, GEMM_BK);
+  if (lda < K || ldw < K || (lda % 8) || (ldw % 8)) return fail(SSP2_EINVAL, "linear_ex: lda=%d ldw=%d must be >= K and multiples of 8", lda, ldw);
+  if (kernel < 0 || kernel > 2) return fail(SSP2_EINVAL, "linear_ex: kernel selector %d", kernel);
+  if (rev < 0 || rev > 1) return fail(SSP2_EINVAL, "linear_ex: rev=%d", rev);
+  if (xin_dev && epilogue != SSP2_EPI_RESID) return fail(SSP2_EINVAL, "linear_ex: xin goes with the residual epilogue only");
+  if (out2_dev && epilogue != SSP2_EPI_GELU) return fail(SSP2_EINVAL, "linear_ex: out2 (the pre-GELU copy) goes with the GELU epilogue only");
+  if (out2_dev && kernel == 2) return fail(SSP2_EINVAL, "linear_ex: out2 is a form of the 128 x 128 kernel (kernel=2 refused)");
+  if (score_site < 0 || score_site > 2 || (score_site && epilogue != SSP2_EPI_GELU)) return fail(SSP2_EINVAL, "linear_ex: score_site=%d (1 / 2 with the GELU epilogue only)", score_site);
+  if (score_site) {
+    if (tokens < GEMM_BM) return fail(SSP2_EINVAL, "linear_ex: the scoring epilogue needs tokens >= %d (tokens=%d)", GEMM_BM, tokens);
+    if (!slab_dev || slab_ld <= 0 || slab_ld > N) return fail(SSP2_EINVAL, "linear_ex: slab / slab_ld=%d (1..N)", slab_ld);
+    if (group < 0 || n_img <= 0) return fail(SSP2_EINVAL, "linear_ex: group=%d n_img=%d", group, n_img);
+    if (total_rows(make_rowmap(tokens, n_img, group), n_img) > M)
+      return fail(SSP2_EINVAL, "linear_ex: %d images of %d tokens in groups of %d exceed M=%d rows", n_img, tokens, group, M);
+  }
+  if (int rc = check_linear_out("linear_ex", epilogue, out_dev, ldo, 8, x_dev, ldx, N)) return rc;
+  ssp2_engine e = op_engine(hip_stream, rev);
+  if (kernel == 1) e.opt[SSP2_OPT_BIG_TILES] = 0;
+  if (kernel == 2) e.opt[SSP2_OPT_BIG_TILE_MIN_ROWS] = 1;
+  GemmArgs g = gemm_operands(act_bf16((const bf16*)a_dev, lda), w_dev, ldw, nullptr, bias_dev, M, N, K, ceil_to(N, 256) / GEMM_BN);
+  g.out = (bf16*)out_dev; g.out2 = (bf16*)out2_dev; g.ldo = ldo; g.x = x_dev; g.xin = xin_dev; g.ldx = ldx;
+  if (score_site) {
+    const RowMap rm = make_rowmap(tokens, n_img, group);
+    g.score_site = score_site; g.tokens = tokens; g.slab = slab_dev; g.slab_ld = slab_ld; g.n_img = n_img; g.group = rm.group; g.mpad = rm.mpad;
+    // the slab has an entry per 128 rows of ceil256(M): the 256 x 256 kernel writes both entries of its last tile, the 128 x 128 kernel
+    // has no tile for an odd last one — it is zeroed here, so that both leave the same slab
+    const int t128 = (M + GEMM_BM - 1) / GEMM_BM;
+    if (t128 & 1) HIPCHK(hipMemsetAsync(slab_dev + (size_t)t128 * 2 * slab_ld, 0, (size_t)2 * slab_ld * sizeof(float), e.stream));
+  }
+  return dispatch_gemm(&e, epilogue, false, g, -2);
+}
+
 // The fp8 projection operator on its own: the forward's launch_gemm256<EPI, SCORE, true> (QKV, fc1 with its score sites, the
 // residual projections) on caller-owned e4m3 operands.  Every argument is checked before the device is touched.
 int ssp2_linear_e4m3(void* hip_stream, int epilogue, const uint8_t* a_dev, int lda, const float* ascale_dev, float ascale_const,

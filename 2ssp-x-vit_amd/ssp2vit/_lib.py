@@ -25,7 +25,7 @@ SYMBOLS = [
     "ssp2_tokens", "ssp2_rows", "ssp2_workspace_bytes", "ssp2_preproc_create", "ssp2_preproc_run", "ssp2_preproc_destroy",
     "ssp2_fp8_calibrate_begin", "ssp2_fp8_calibrate_end", "ssp2_fp8_attn_scale", "ssp2_fp8_set_attn_scale",
     "ssp2_create_opts", "ssp2_attention_stream_bf16", "ssp2_create_ext", "ssp2_attention_prefix_bf16",
-    "ssp2_set_layer_scale", "ssp2_linear_ls_bf16", "ssp2_linear_ls_e4m3",
+    "ssp2_set_layer_scale", "ssp2_linear_ls_bf16", "ssp2_linear_ls_e4m3", "ssp2_linear_bf16_ex",
 ]
 
 T_KINDS = ["patch_w", "patch_b", "cls", "pos", "ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b",
@@ -230,6 +230,7 @@ def load(build_if_missing: bool = True, variant: Optional[str] = None) -> C.CDLL
     lib.ssp2_load_tensor_dev.argtypes = [vp, i32, i32, vp, C.c_size_t]
     lib.ssp2_load_tensors_dev.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp), C.POINTER(C.c_size_t)]
     lib.ssp2_linear_bf16.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, vp, i32, i32]
+    lib.ssp2_linear_bf16_ex.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32]
     lib.ssp2_linear_e4m3.argtypes = [vp, i32, vp, i32, vp, C.c_float, vp, i32, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32]
     lib.ssp2_set_layer_scale.argtypes = [vp, i32, i32, vp, i32]
     lib.ssp2_linear_ls_bf16.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32]

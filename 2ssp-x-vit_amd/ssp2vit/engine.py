@@ -487,6 +487,75 @@ class VitEngine:
                                         {"auto": 0, "small": 1, "big": 2}[kernel]))
         return x if epi == 1 else out
 
+    def linear_ex(self, a: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], epilogue: str = "bf16", *,
+                  rows: Optional[int] = None, kernel: str = "auto", out: Optional[torch.Tensor] = None, out2: Optional[torch.Tensor] = None,
+                  x: Optional[torch.Tensor] = None, xin: Optional[torch.Tensor] = None, rev: int = 0, score_site: int = 0,
+                  tokens: int = 0, group: int = 0, n_img: int = 0, slab_ld: Optional[int] = None):
+        """`linear` on the caller's own buffers, with every form the forward's bf16 launches take (ssp2_linear_bf16_ex).  a: bf16
+        row-major device tensor [>= rows, >= K] (rows = a.shape[0] by default), read at its row stride.  weight [N, K]: a bf16
+        row-major device tensor is read WHERE IT IS at its row stride — the storage behind it must reach ceil256(N) rows, rows N..
+        being zero (the kernels read whole column tiles); anything else is rounded to bf16 and padded like `linear` does.  bias [N] or
+        None.  out / out2 (bf16) and x / xin (f32) are row-major device tensors of >= [rows, N], written / read at their row strides
+        (out2 at out's, xin at x's).  epilogue "bf16" / "gelu" -> out (allocated [rows, N] when None); "gelu" with out2: the
+        pre-GELU bf16 copy as well (128 x 128 kernel); "resid" -> x = xin (default x) + bf16(...), returned.  score_site 1 / 2
+        ("gelu"; tokens, group, n_img: the row layout of ssp2_rows) returns (out, slab f32 [2 * ceil(rows / 256), 2, slab_ld]),
+        slab_ld defaulting to N, pre-filled with NaN: entry t covers rows 128 t .. 128 t + 127.  rev: the walk direction of the tiles."""
+        epi = {"bf16": 0, "resid": 1, "gelu": 2}[epilogue]
+        N, K = weight.shape
+        M = a.shape[0] if rows is None else int(rows)
+        npad = (N + 255) // 256 * 256
+        if (out2 is not None or score_site) and epi != 2:
+            raise ValueError("out2 / score_site go with the gelu epilogue only")
+        if (xin is not None and epi != 1) or (x is not None and epi != 1) or (out is not None and epi == 1):
+            raise ValueError("x / xin go with the resid epilogue, out with the others")
+
+        def dev2d(name, t, dtype, r, c):
+            if t.device.type != "cuda" or t.dtype != dtype or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] < r or t.shape[1] < c:
+                raise ValueError(f"{name} must be a row-major {dtype} device tensor of >= [{r}, {c}]")
+        dev2d("a", a, torch.bfloat16, M, K)
+        if weight.device.type == "cuda" and weight.dtype == torch.bfloat16 and weight.dim() == 2 and weight.stride(1) == 1:
+            wp, ldw = weight, weight.stride(0)
+            if weight.storage_offset() + (npad - 1) * ldw + K > weight.untyped_storage().nbytes() // 2:
+                raise ValueError(f"the storage behind weight must hold ceil256(N) = {npad} rows (rows past N zero)")
+        else:
+            wp = torch.zeros(npad, K, dtype=torch.bfloat16, device=self.device)
+            wp[:N].copy_(weight.to(self.device, torch.bfloat16))
+            ldw = K
+        bp = torch.zeros(npad, dtype=torch.float32, device=self.device)
+        if bias is not None:
+            bp[:N].copy_(bias.to(self.device, torch.bfloat16).float())
+        slab = None
+        ldo = ldx = 0
+        if epi == 1:
+            if x is None:
+                raise ValueError("resid epilogue needs x")
+            for name, t in (("x", x), ("xin", xin)):
+                if t is not None:
+                    dev2d(name, t, torch.float32, M, N)
+            if xin is not None and xin.stride(0) != x.stride(0):
+                raise ValueError("xin must have x's row stride (the kernel reads both at ldx)")
+            ldx = x.stride(0)
+        else:
+            if out is None:
+                out = torch.empty(M, N, dtype=torch.bfloat16, device=self.device)
+            for name, t in (("out", out), ("out2", out2)):
+                if t is not None:
+                    dev2d(name, t, torch.bfloat16, M, N)
+            if out2 is not None and out2.stride(0) != out.stride(0):
+                raise ValueError("out2 must have out's row stride (the kernel writes both at ldo)")
+            ldo = out.stride(0)
+            if score_site:
+                slab_ld = N if slab_ld is None else int(slab_ld)
+                slab = torch.full((2 * ((M + 255) // 256), 2, slab_ld), float("nan"), dtype=torch.float32, device=self.device)
+        self._check(self.lib.ssp2_linear_bf16_ex(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), epi, _ptr(a), a.stride(0),
+                                                 _ptr(wp), ldw, _ptr(bp), M, N, K, _ptr(out) if epi != 1 else None, ldo,
+                                                 _ptr(out2) if epi == 2 else None, _ptr(x) if epi == 1 else None,
+                                                 _ptr(xin) if epi == 1 else None, ldx, int(score_site), int(tokens), int(group),
+                                                 int(n_img), _ptr(slab), slab_ld or 0, {"auto": 0, "small": 1, "big": 2}[kernel], int(rev)))
+        if epi == 1:
+            return x
+        return (out, slab) if score_site else out
+
     def _gamma_vec(self, gamma: torch.Tensor, N: int) -> torch.Tensor:
         """A LayerScale operand of the operator entries: fp32 [N] on the device, padded to 256 like a bias, values untouched."""
         if gamma.numel() != N:

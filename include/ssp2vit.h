@@ -304,6 +304,24 @@ enum { SSP2_EPI_BF16 = 0, SSP2_EPI_RESID = 1, SSP2_EPI_GELU = 2 };
 int ssp2_linear_bf16(void* hip_stream, int epilogue, const uint16_t* a_dev, int lda, const uint16_t* w_dev, int ldw,
                      const float* bias_dev, int M, int N, int K, uint16_t* out_dev, int ldo, float* x_dev, int ldx, int kernel);
 
+/* Additive (ABI stays 7): ssp2_linear_bf16 with everything else the forward's bf16 launches set — operands, layouts, epilogues and checks as
+ * there (rows of a_dev past M and columns past K are never read, rows of out / x past M and columns past N never written), plus:
+ *   xin_dev   (RESID only) x_dev[M, ldx] = xin_dev[M, ldx] + float(bf16(acc + bias)); NULL: x_dev, in place.  With xin_dev, x_dev is
+ *             written and never read.
+ *   out2_dev  (GELU only) bf16 [M, ldo]: also the pre-GELU value bf16(acc + bias), the operand of the unfused hook.  A form of the
+ *             128 x 128 kernel: kernel = 0 routes to it whatever M is, kernel = 2 is refused.
+ *   score_site 1 / 2 (GELU only, tokens >= 128): also the stage-1 slab [2 * ceil(M / 256)][2][slab_ld] f32, 1 <= slab_ld <= N, every
+ *             entry written — per 128-row tile and segment (the rows of the tile's first / second image in the layout (tokens, group,
+ *             n_img) of ssp2_rows, which must fit in M; the layout's pad rows and, with group > 0, rows behind the last image count
+ *             nowhere) the fp32 sum of squares of bf16(acc + bias) (site 1) or of the bf16 GELU output (site 2); zeros where no row
+ *             counts.  Columns at and past slab_ld of an entry do not exist.  Both kernels give the same bits.
+ *   rev       walk direction of the 256 x 256 kernel's tiles (0 / 1; the forward alternates them), the same bits either way.
+ * Every argument is checked before the device is touched. */
+int ssp2_linear_bf16_ex(void* hip_stream, int epilogue, const uint16_t* a_dev, int lda, const uint16_t* w_dev, int ldw,
+                        const float* bias_dev, int M, int N, int K, uint16_t* out_dev, int ldo, uint16_t* out2_dev,
+                        float* x_dev, const float* xin_dev, int ldx,
+                        int score_site, int tokens, int group, int n_img, float* slab_dev, int slab_ld, int kernel, int rev);
+
 /* Additive (ABI stays 7): the fp8 mode's projection on its own — the 256 x 256 kernel on e4m3 operands (OCP fp8 bytes), the very launches of the
  * forward's QKV, fc1 (+ score sites) and residual projections, on caller-owned device buffers:
  *   a_dev e4m3 [M, lda] (K used; rows past M never read), w_dev e4m3 [ceil256(N), ldw] (rows past N: zero bytes),

@@ -343,6 +343,53 @@ def test_fp8_operator_entries_refuse_bad_arguments_before_touching_the_device():
         eng.linear_e4m3(a8.float(), w8, torch.ones(64), None)
 
 
+def test_bf16_ex_operator_entry_refuses_bad_arguments_before_touching_the_device():
+    """ssp2_linear_bf16_ex checks every argument before the first HIP call: each bad call comes back SSP2_EINVAL (-1) with a message;
+    the valid baselines get past the checks (SSP2_EHIP, -2, on a machine without a GPU; none of them is run where there is one: the
+    pointers are dummies)."""
+    import ctypes as C
+    from ssp2vit import _lib
+    from ssp2vit.engine import VitEngine
+    lib = _lib.load()
+    hdr = open(os.path.join(ROOT, "include", "ssp2vit.h")).read()
+    assert "ssp2_linear_bf16_ex" in _lib.SYMBOLS and hasattr(lib, "ssp2_linear_bf16_ex") and "int ssp2_linear_bf16_ex(" in hdr
+    assert lib.ssp2_abi_version() == 7
+    P = C.c_void_p(4096)
+
+    def lin(epi=0, a=P, lda=768, w=P, ldw=768, bias=P, M=4096, N=2304, K=768, out=P, ldo=2304, out2=None, x=None, xin=None, ldx=0,
+            site=0, tokens=0, group=0, n_img=0, slab=None, slab_ld=0, kernel=0, rev=0):
+        return lib.ssp2_linear_bf16_ex(None, epi, a, lda, w, ldw, bias, M, N, K, out, ldo, out2, x, xin, ldx, site, tokens, group, n_img,
+                                       slab, slab_ld, kernel, rev)
+    gelu = dict(epi=2, N=3072, ldo=3072)
+    score = dict(gelu, site=1, tokens=197, n_img=20, slab=P, slab_ld=3072)
+    resid = dict(epi=1, N=768, out=None, ldo=0, x=P, ldx=768)
+    if not torch.cuda.is_available():
+        for ok in (dict(), dict(lda=776, ldw=776, ldo=2312), dict(K=64, M=1, N=64, ldo=64), gelu, dict(gelu, out2=P), dict(gelu, out2=P, kernel=1),
+                   score, dict(score, out2=P), dict(score, site=2, group=4, n_img=4, slab_ld=1), dict(score, kernel=2), resid,
+                   dict(resid, xin=P, ldx=772), dict(rev=1, kernel=2)):
+            assert lin(**ok) == -2, ok
+    bad = [dict(a=None), dict(w=None), dict(bias=None), dict(M=0), dict(N=0), dict(K=0), dict(K=736, lda=736, ldw=736),
+           dict(N=2336, ldo=2336), dict(lda=704), dict(lda=772), dict(ldw=704), dict(ldw=772), dict(kernel=3), dict(kernel=-1),
+           dict(rev=2), dict(rev=-1), dict(epi=3), dict(epi=-1), dict(out=None), dict(ldo=2300), dict(ldo=2308), dict(gelu, out=None),
+           dict(xin=P), dict(gelu, xin=P), dict(out2=P), dict(resid, out2=P), dict(gelu, out2=P, kernel=2), dict(site=1),
+           dict(resid, site=1), dict(gelu, site=3), dict(gelu, site=-1), dict(score, tokens=127), dict(score, slab=None),
+           dict(score, slab_ld=0), dict(score, slab_ld=3073), dict(score, n_img=21), dict(score, group=4, n_img=20),
+           dict(score, group=-1), dict(score, n_img=0), dict(resid, x=None), dict(resid, ldx=764), dict(resid, ldx=770)]
+    for kw in bad:
+        assert lin(**kw) == -1, kw
+        assert lib.ssp2_last_error(), kw
+
+    # the wrapper refuses host tensors, other dtypes and undersized buffers before any call (an engine object without a device)
+    eng = VitEngine.__new__(VitEngine)
+    eng.lib = lib
+    a, w = torch.zeros(256, 128, dtype=torch.bfloat16), torch.zeros(64, 128)
+    for kw in (dict(), dict(rows=257), dict(epilogue="resid"), dict(epilogue="bf16", out2=a), dict(epilogue="bf16", score_site=1)):
+        with pytest.raises(ValueError):
+            eng.linear_ex(a, w, None, **kw)
+    with pytest.raises(ValueError):
+        eng.linear_ex(a.float(), w, None)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
 def test_product_path_fails_loudly_without_gpu():
     from oracle.vit_modules import build_from_flat
