@@ -79,6 +79,8 @@ def run_one(args, target, run_id):
     rank0 = pg is None or torch.distributed.get_rank() == 0
     vp.DEFAULT_PRECISION = "bf16"          # (module-level switch: a previous fp8 run in this process must not leak into this one's set-up)
     vp.DEFAULT_ATTN_STREAM = 1 if args.long_sequences else None      # None: the environment's SSP2_ATTN_STREAM
+    # --long-sequences --precision fp8: the user asked for both, so the streaming engines accept fp8 (SSP2_OPT_STREAM_FP8)
+    vp.DEFAULT_STREAM_FP8 = True if (args.long_sequences and args.precision == "fp8") else None      # None: the environment's SSP2_STREAM_FP8
     if args.weights:
         # a LOCAL checkpoint (reference :636-667 loads its model with from_pretrained / timm.create_model; the network
         # fetches stay out): .safetensors / .pth state dict or an HF save_pretrained directory, any of the three key layouts
@@ -334,7 +336,8 @@ def build_argparser():
                                                            "does (default: one walk whose dense forward serves both; a reshuffling loader then feeds both stages the same order)")
     p.add_argument("--long-sequences", action="store_true",
                    help="models with more than 288 tokens (384-pixel /16: 577, patch 8: 785) on the key-streaming attention kernel "
-                        "(the engines' attn_stream = 1, as SSP2_ATTN_STREAM=1); without it such a model is refused when its engine is created")
+                        "(the engines' attn_stream = 1, as SSP2_ATTN_STREAM=1); without it such a model is refused when its engine is created.  "
+                        "With --precision fp8 it also sets the engines' stream_fp8 (as SSP2_STREAM_FP8=1): the streaming attention then writes e4m3")
     p.add_argument("--fp8-calibrate", action="store_true", help="with --precision fp8: measure the attention outputs of the first calibration images and set the e4m3 hand-off scales")
     # accepted and ignored (data / fine-tuning flags of the reference that need the network)
     for flag in ("--load-cifar", "--do-finetune", "--freeze-backbone", "--replace-classifier", "--use-adapter", "--save-adapter",

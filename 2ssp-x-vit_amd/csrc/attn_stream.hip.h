@@ -1,5 +1,6 @@
 // Key-streaming attention, d_h = 64, for sequences the resident kernels of attn.hip.h cannot hold (more than 288 tokens:
-// 384-pixel /16 models with 577 tokens, patch-8 models with 785, ...).  bf16 in and out, f32 accumulation, online softmax.
+// 384-pixel /16 models with 577 tokens, patch-8 models with 785, ...).  bf16 in, bf16 (or, full form, e4m3) out, f32 accumulation,
+// online softmax.
 //
 // Full form (attn64_stream_kernel): one 5-wave workgroup per (image, head, block of four 32-query tiles).  Waves 0..3 are the
 // consumers (one query tile each), wave 4 is the producer: it streams K and V through LDS in stages of 128 keys (four 32-key
@@ -19,13 +20,18 @@
 // key tiles wholly past `tokens` are neither loaded nor multiplied.  Query rows past `tokens` are clamped and never stored.
 // The output goes through a wave-private [32 queries][128 B] LDS tile (placed in the ring buffer the last stage does not use) as
 // whole 128-byte row segments.
+// OUT8 form (attn64_stream_kernel<true>, the fp8 mode's out-projection operand): the same main loop, and instead of the bf16 tile the
+// e4m3(o * out8_scale) bytes of the fp32 accumulator, by the rule of attn64_persist_kernel: the wave's [32 queries][64 B] tile through
+// the same staging slot (a lane's four consecutive d_h are one dword), then 128 sixteen-byte row pieces, two per lane; a wave that
+// clipped a value adds 1 to *sat_counter.  No bf16 output is written.  attn64_stream_kernel<false> is the bf16 kernel as it was.
 //
 // CLS-only form (attn64_stream_cls_kernel<P>, the evaluation tail): P = 1 or 2 prefix queries per (image, head) against every key.  One
 // wave per item, four items per workgroup: lane <-> key for the scores (chunks of 64 keys, online max / sum as above, f32 probabilities), then
 // lane <-> d_h for P V (the chunk's probabilities broadcast by ds_bpermute).  q from the compact [n, q_img_stride] buffer, output to
 // the compact [n, o_img_stride] buffer, as attn_fwd_kernel<64, NT, true>.
 //
-// Neither form writes e4m3 (no fp8 out-projection operand): an fp8 engine keeps its out-projection on bf16 on this route.
+// The CLS-only form writes bf16 only (the evaluation tail stays bf16 in fp8 mode).  A streaming engine refuses fp8 unless
+// SSP2_OPT_STREAM_FP8 is set; with it the full form feeds the e4m3 out-projection (SSP2_OPT_FP8_PROJ) as the persistent kernels do.
 #pragma once
 #include "attn.hip.h"          // attn_f32x2, the common helpers
 
@@ -36,8 +42,11 @@
 #define ATTN_STREAM_SMEM (2 * ATTN_STREAM_STAGE)                            // double-buffered ring (64 KiB)
 static_assert(ATTN_STREAM_QW * 4096 <= ATTN_STREAM_STAGE, "the output staging tiles live in one ring buffer");
 
+template <bool OUT8>
 __global__ __launch_bounds__(64 * (ATTN_STREAM_QW + 1), 2) void attn64_stream_kernel(const bf16* __restrict__ qkv, int ld, bf16* __restrict__ out, int ldo,
-                                                                                    int tokens, int dim, int heads, int qblocks, float scale, RowMap rm) {
+                                                                                    int tokens, int dim, int heads, int qblocks, float scale, RowMap rm,
+                                                                                    uint8_t* __restrict__ out8, int ldo8, unsigned int* __restrict__ sat_counter,
+                                                                                    float out8_scale) {
   constexpr int QW = ATTN_STREAM_QW, KTS = ATTN_STREAM_KTS, SK = KTS * 32, KV = SK * 128, STAGE = ATTN_STREAM_STAGE;
   constexpr int KS = 4, DT = 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -196,6 +205,29 @@ __global__ __launch_bounds__(64 * (ATTN_STREAM_QW + 1), 2) void attn64_stream_ke
   // staging tile in the ring buffer the last stage did not use: it held stage ns - 2 (finished by every consumer before B(ns - 1))
   // or nothing, and the producer issues nothing after B(ns - 1)
   char* const ost = smem + (((ns - 1) & 1) ^ 1) * STAGE + wave * 4096;
+  if constexpr (OUT8) {
+    // e4m3 bytes (attn64_persist_kernel's rule): row q of the tile = 64 B at ost + q * 64, the lane's dword at d_h = 32 dt + 8 g4 + 4 lh
+    const float sc8 = inv * out8_scale;
+    bool sat8 = false;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4)
+        *(uint32_t*)(ost + l31 * 64 + dt * 32 + 8 * g4 + 4 * lh) = pack_e4m3x4_sat(oacc[dt][4 * g4] * sc8, oacc[dt][4 * g4 + 1] * sc8,
+                                                                                 oacc[dt][4 * g4 + 2] * sc8, oacc[dt][4 * g4 + 3] * sc8, sat8);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    f32x4 o8[2];
+#pragma unroll
+    for (int r2 = 0; r2 < 2; ++r2) o8[r2] = *(const f32x4*)(ost + (r2 * 64 + lane) * 16);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int r2 = 0; r2 < 2; ++r2) {
+      const int c = r2 * 64 + lane, qq = qt * 32 + (c >> 2);
+      if (qq < tokens) *(f32x4*)(out8 + (r0 + qq) * (size_t)ldo8 + head * 64 + (c & 3) * 16) = o8[r2];
+    }
+    report_sat(sat8, sat_counter);            // (padding queries repeat the last token's row: they cannot saturate alone)
+    return;
+  }
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt)
 #pragma unroll

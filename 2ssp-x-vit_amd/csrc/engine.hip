@@ -117,7 +117,7 @@ struct ssp2_engine {
   int zig_hold = -1;       // >= 0: the launches of a split operation all take this direction (next_dir does not advance)
   // Run-time switches (ssp2_set_option).  Their defaults are read from the environment ONCE, in ssp2_create (round 2 called
   // getenv on every launch); tests and A/B scripts flip them per handle.
-  int opt[SSP2_OPT_COUNT] = {};
+  int opt[SSP2_OPT_END] = {};
   std::vector<void*> allocs;
   int arena_mode = 0;                       // ssp2_create: 1 = measuring pass, 2 = assigning pass (dalloc)
   size_t arena_need[2] = {0, 0};            // [0] zero-initialised, [1] written before read
@@ -535,20 +535,23 @@ static bool attn_stream_ok(int dh, int tokens) { return dh == 64 && tokens >= 1 
 static bool attn_streams(int mode, int dh, int tokens) {
   return attn_stream_ok(dh, tokens) && (mode >= 2 || (mode == 1 && !attn_resident(dh, tokens)));
 }
-// which geometries have a persistent kernel (the ones that can write the e4m3 output); never the streaming route
+// which geometries have a persistent kernel (they can write the e4m3 output); never the streaming route
 static bool attn_persistent_for(int stream, int persist, int dh, int tokens) {
   const int nt = (tokens + 31) / 32;
   if (attn_streams(stream, dh, tokens)) return false;
   return persist && ((dh == 64 && nt >= 4 && nt <= 7) || (dh == 80 && nt == 9 && tokens == 257));
 }
 static bool attn_persistent(const ssp2_engine* e) { return attn_persistent_for(e->opt[SSP2_OPT_ATTN_STREAM], e->opt[SSP2_OPT_ATTN_PERSIST], e->dh, e->tokens); }
+static bool attn_streaming(const ssp2_engine* e) { return attn_streams(e->opt[SSP2_OPT_ATTN_STREAM], e->dh, e->tokens); }
+// "this engine's full attention can write e4m3": a persistent kernel, or the key-streaming kernel's OUT8 form (SSP2_OPT_STREAM_FP8)
+static bool attn_writes_e4m3(const ssp2_engine* e) { return attn_persistent(e) || (attn_streaming(e) && e->opt[SSP2_OPT_STREAM_FP8]); }
 // geometries launch_attn below has a kernel for under the streaming mode `stream` — checked when an engine is created, so that an
 // unsupported geometry fails THERE and not at the first forward
 static bool attn_supported(int dh, int tokens, int stream = 0) {
   return attn_resident(dh, tokens) || attn_streams(stream, dh, tokens);
 }
 // the key-streaming kernels (attn_stream.hip.h): full attention over the slab / dense rows, or the CLS-only tail
-static int launch_attn_stream(ssp2_engine* e, int n, RowMap rm, bool cls_only) {
+static int launch_attn_stream(ssp2_engine* e, int n, RowMap rm, bool cls_only, uint8_t* out8 = nullptr, float out8_scale = ATTN_OUT8_SCALE) {
   const int D = e->d.dim, ld = 3 * D, ldo = e->o_ld > 0 ? e->o_ld : D, T = e->tokens;
   const double qn = cls_only ? (double)e->tail_rows : (double)T;
   ProfScope ps(e, SSP2_K_ATTN, 4.0 * qn * T * 64 * e->d.heads * n, 2.0 * n * D * (2.0 * T + 2.0 * qn));
@@ -565,21 +568,26 @@ static int launch_attn_stream(ssp2_engine* e, int n, RowMap rm, bool cls_only) {
   } else {
     const int qblocks = (T + 32 * ATTN_STREAM_QW - 1) / (32 * ATTN_STREAM_QW);
     if (items * qblocks > 0x7fffffffL) return fail(SSP2_EINVAL, "too many attention items");
-    static bool attr_done[kMaxDevices] = {};
-    if (!attr_done[e->dev]) {
-      HIPCHK(hipFuncSetAttribute((const void*)attn64_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_STREAM_SMEM));
-      attr_done[e->dev] = true;
+    static bool attr_done[2][kMaxDevices] = {};
+    if (!attr_done[out8 != nullptr][e->dev]) {
+      HIPCHK(hipFuncSetAttribute(out8 ? (const void*)attn64_stream_kernel<true> : (const void*)attn64_stream_kernel<false>,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_STREAM_SMEM));
+      attr_done[out8 != nullptr][e->dev] = true;
     }
-    hipLaunchKernelGGL(attn64_stream_kernel, dim3((unsigned)(items * qblocks)), dim3(64 * (ATTN_STREAM_QW + 1)), ATTN_STREAM_SMEM, e->stream,
-                       e->qkvbuf, ld, e->obuf, ldo, T, D, e->d.heads, qblocks, scale, rm);
+    if (out8)   // the e4m3 bytes of the fp8 out-projection's operand instead of the bf16 output (SSP2_OPT_STREAM_FP8)
+      hipLaunchKernelGGL(attn64_stream_kernel<true>, dim3((unsigned)(items * qblocks)), dim3(64 * (ATTN_STREAM_QW + 1)), ATTN_STREAM_SMEM, e->stream,
+                         e->qkvbuf, ld, (bf16*)nullptr, ldo, T, D, e->d.heads, qblocks, scale, rm, out8, e->ld8_dim, e->fp8_sat, out8_scale);
+    else
+      hipLaunchKernelGGL(attn64_stream_kernel<false>, dim3((unsigned)(items * qblocks)), dim3(64 * (ATTN_STREAM_QW + 1)), ATTN_STREAM_SMEM, e->stream,
+                         e->qkvbuf, ld, e->obuf, ldo, T, D, e->d.heads, qblocks, scale, rm, (uint8_t*)nullptr, 0, (unsigned int*)nullptr, 0.f);
   }
   HIPCHK(hipGetLastError());
   return 0;
 }
 static int launch_attn(ssp2_engine* e, int n, RowMap rm, bool cls_only = false, uint8_t* out8 = nullptr, float out8_scale = ATTN_OUT8_SCALE) {
-  if (attn_streams(e->opt[SSP2_OPT_ATTN_STREAM], e->dh, e->tokens)) {
-    if (out8) return fail(SSP2_ESTATE, "the key-streaming attention writes bf16 only (no e4m3 output)");
-    return launch_attn_stream(e, n, rm, cls_only);
+  if (attn_streaming(e)) {
+    if (out8 && (cls_only || !e->opt[SSP2_OPT_STREAM_FP8])) return fail(SSP2_ESTATE, "the key-streaming attention writes bf16 only (no e4m3 output)");
+    return launch_attn_stream(e, n, rm, cls_only, out8, out8_scale);
   }
   const int nt = (e->tokens + 31) / 32;
 #define ATTN_CASE(DH_, NT_) if (e->dh == DH_ && nt == NT_) return cls_only ? launch_attn_t<DH_, NT_, true>(e, n, rm) : launch_attn_t<DH_, NT_, false>(e, n, rm, out8, out8_scale)
@@ -668,6 +676,7 @@ int ssp2_create_ext(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_vi
     e->opt[SSP2_OPT_DEFER_RESID] = 0;
 #endif
     e->opt[SSP2_OPT_ATTN_STREAM] = std::max(0, std::min(2, env_int("SSP2_ATTN_STREAM", 0)));
+    e->opt[SSP2_OPT_STREAM_FP8] = env_int("SSP2_STREAM_FP8", 0) ? 1 : 0;
   }
   if (opt) {   // explicit overrides go through the same checks as ssp2_set_option (the geometry is not known yet: checked below)
     for (int i = 0; i < SSP2_OPT_COUNT; ++i) {
@@ -859,7 +868,7 @@ int ssp2_set_cu_limit(ssp2_handle e, int n_cu) {
 }
 int ssp2_set_option(ssp2_handle e, int option, int value) {
   if (!e) return fail(SSP2_EINVAL, "null handle");
-  if (option < 0 || option >= SSP2_OPT_COUNT) return fail(SSP2_EINVAL, "unknown option %d", option);
+  if (option < 0 || option >= SSP2_OPT_END) return fail(SSP2_EINVAL, "unknown option %d", option);
   if (option == SSP2_OPT_LN_FUSION && (value < 0 || value > 2)) return fail(SSP2_EINVAL, "SSP2_OPT_LN_FUSION takes 0, 1 or 2");
   if (option == SSP2_OPT_GROUP256 && value < 0) return fail(SSP2_EINVAL, "SSP2_OPT_GROUP256 takes 100 * GM + GN >= 0");
   if (option == SSP2_OPT_BIG_TILE_MIN_ROWS && value < 256) return fail(SSP2_EINVAL, "SSP2_OPT_BIG_TILE_MIN_ROWS takes >= 256 rows");
@@ -872,13 +881,18 @@ int ssp2_set_option(ssp2_handle e, int option, int value) {
     if (value < 0 || value > 2) return fail(SSP2_EINVAL, "SSP2_OPT_ATTN_STREAM takes 0, 1 or 2");
     if (!attn_supported(e->dh, e->tokens, value))
       return fail(SSP2_ESTATE, "SSP2_OPT_ATTN_STREAM = %d: head dim %d with %d tokens has no resident attention kernel", value, e->dh, e->tokens);
-    if (e->fp8 && attn_streams(value, e->dh, e->tokens)) return fail(SSP2_ESTATE, "SSP2_OPT_ATTN_STREAM = %d: the key-streaming attention is bf16 only (engine is in fp8)", value);
+    if (e->fp8 && attn_streams(value, e->dh, e->tokens) && !e->opt[SSP2_OPT_STREAM_FP8]) return fail(SSP2_ESTATE, "SSP2_OPT_ATTN_STREAM = %d: the key-streaming attention is bf16 only (engine is in fp8)", value);
+  }
+  if (option == SSP2_OPT_STREAM_FP8) {
+    if (value < 0 || value > 1) return fail(SSP2_EINVAL, "SSP2_OPT_STREAM_FP8 takes 0 or 1");
+    if (!value && e->fp8 && attn_streaming(e))
+      return fail(SSP2_ESTATE, "SSP2_OPT_STREAM_FP8 = 0: this engine is in fp8 on the key-streaming attention (SSP2_OPT_FP8_PROJ = 0 keeps its attention output on bf16)");
   }
   e->opt[option] = value;
   return 0;
 }
 int ssp2_get_option(ssp2_handle e, int option) {
-  if (!e || option < 0 || option >= SSP2_OPT_COUNT) return fail(SSP2_EINVAL, "bad option query");
+  if (!e || option < 0 || option >= SSP2_OPT_END) return fail(SSP2_EINVAL, "bad option query");
   return e->opt[option];
 }
 int ssp2_tokens(ssp2_handle e) { return e ? e->tokens : SSP2_EINVAL; }
@@ -1097,7 +1111,7 @@ int ssp2_set_precision(ssp2_handle e, int mode) {
   if (!e) return fail(SSP2_EINVAL, "null handle");
   if (mode == SSP2_PREC_BF16) { e->fp8 = false; return 0; }
   if (mode != SSP2_PREC_FP8) return fail(SSP2_EINVAL, "unknown precision %d", mode);
-  if (attn_streams(e->opt[SSP2_OPT_ATTN_STREAM], e->dh, e->tokens))
+  if (attn_streaming(e) && !e->opt[SSP2_OPT_STREAM_FP8])
     return fail(SSP2_ESTATE, "set_precision(fp8): this engine runs the key-streaming attention (SSP2_OPT_ATTN_STREAM = %d, %d tokens), which is bf16 only",
                 e->opt[SSP2_OPT_ATTN_STREAM], e->tokens);
   int rc;
@@ -1230,10 +1244,10 @@ static int attn_half(ssp2_engine* e, LayersCall& c, int l) {
   GemmArgs q = bind(L.qkv, hbuf_operand(e, c.f8), M, 3 * D);
   q.out = e->qkvbuf; q.ldo = 3 * D;
   if ((rc = dispatch_gemm(e, EPI_BF16, c.f8, q, SSP2_K_GEMM_QKV))) return rc;
-  // fp8 out-projection (SSP2_OPT_FP8_PROJ): the persistent attention kernel writes e4m3(o * 16) bytes, the projection runs on
-  // e4m3 operands and divides the 16 out in its epilogue
+  // fp8 out-projection (SSP2_OPT_FP8_PROJ): the persistent attention kernel (or, SSP2_OPT_STREAM_FP8, the key-streaming one) writes
+  // e4m3(o * 16) bytes, the projection runs on e4m3 operands and divides the 16 out in its epilogue
   // (during ssp2_fp8_calibrate_* the projection stays on bf16 and the block's max |o| is recorded)
-  const bool f8_proj = c.f8 && e->opt[SSP2_OPT_FP8_PROJ] && attn_persistent(e) && has_e4m3(L.proj) && D % 64 == 0 && !e->fp8_calibrating;
+  const bool f8_proj = c.f8 && e->opt[SSP2_OPT_FP8_PROJ] && attn_writes_e4m3(e) && has_e4m3(L.proj) && D % 64 == 0 && !e->fp8_calibrating;
   if ((rc = launch_attn(e, c.n, c.rm, false, f8_proj ? e->obuf8 : nullptr, L.o8_scale))) return rc;
   if (c.f8 && e->fp8_calibrating && e->attn_amax) {
     ProfScope ps(e, SSP2_K_OTHER);
@@ -1879,6 +1893,25 @@ int ssp2_attention_stream_bf16(void* hip_stream, const uint16_t* qkv_dev, int n,
   ssp2_engine e = op_attn_engine(hip_stream, -1, tokens, heads, d_h, qkv_dev, q_cls_dev, out_dev, ldo);
   e.opt[SSP2_OPT_ATTN_STREAM] = 2;
   return launch_attn_stream(&e, n, make_rowmap(tokens, n, group), q_cls_dev != nullptr);
+}
+
+// ... its OUT8 form (attn64_stream_kernel<true>): e4m3(o * out8_scale) bytes, the clipping waves counted into *sat_dev (may be null)
+int ssp2_attention_stream_e4m3(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
+                               uint8_t* out8_dev, int ldo8, float out8_scale, unsigned int* sat_dev) {
+  if (!qkv_dev || !out8_dev) return fail(SSP2_EINVAL, "attention_stream_e4m3: null qkv / out8");
+  if (int rc = check_attn_args("attention_stream_e4m3", n, tokens, heads, d_h, group, nullptr, 0)) return rc;
+  if (d_h != 64) return fail(SSP2_EINVAL, "attention_stream_e4m3: d_h=%d (64 only)", d_h);
+  if (tokens > ATTN_STREAM_MAX_TOKENS) return fail(SSP2_EINVAL, "attention_stream_e4m3: tokens=%d (1..%d)", tokens, ATTN_STREAM_MAX_TOKENS);
+  if ((long)n * heads * ((tokens + 32 * ATTN_STREAM_QW - 1) / (32 * ATTN_STREAM_QW)) > 0x7fffffffL) return fail(SSP2_EINVAL, "too many attention items");
+  if (ldo8 < heads * 64 || ldo8 % 16 || ((uintptr_t)out8_dev & 15))
+    return fail(SSP2_EINVAL, "attention_stream_e4m3: out8 / ldo8=%d (16-byte aligned, >= dim %d, a multiple of 16)", ldo8, heads * 64);
+  int ex = 0;
+  if (!(out8_scale > 0.f) || !std::isfinite(out8_scale) || frexpf(out8_scale, &ex) != 0.5f)
+    return fail(SSP2_EINVAL, "attention_stream_e4m3: out8_scale must be a power of two > 0 (got %g)", out8_scale);
+  ssp2_engine e = op_attn_engine(hip_stream, -1, tokens, heads, d_h, qkv_dev, nullptr, nullptr, heads * 64);
+  e.opt[SSP2_OPT_ATTN_STREAM] = 2; e.opt[SSP2_OPT_STREAM_FP8] = 1;
+  e.ld8_dim = ldo8; e.fp8_sat = sat_dev;
+  return launch_attn_stream(&e, n, make_rowmap(tokens, n, group), false, out8_dev, out8_scale);
 }
 
 // The tail's prefix-query attention on its own (n_prefix queries per image, prefix-major q and out), on the resident CLS-only kernels or,

@@ -212,6 +212,7 @@ int main(int argc, char** argv) {
   if (argc > 1 && !strcmp(argv[1], "stream")) {
     // attn_bench stream [n] [heads]: the key-streaming kernel at 197 / 257 / 577 / 785 / 1025 tokens next to the resident kernels the
     // engine launches at 197 (attn64_persist_kernel<7, 1>) and 257 (attn_fwd_kernel<64, 9>), on n images x heads; median of 9 launches.
+    // "stream e4m3": its OUT8 form (attn64_stream_kernel<true>: e4m3(o * 16) bytes instead of the bf16 output) on the same inputs.
     // Work = 4 T^2 d_h flops per (image, head) (S = QK^T and O = PV); query.key pairs = T^2 per (image, head).
     hipDeviceProp_t pr; CK(hipGetDeviceProperties(&pr, 0));
     const int nCU = pr.multiProcessorCount;
@@ -226,7 +227,10 @@ int main(int argc, char** argv) {
       for (auto& v : h) v = f2bf((rand() / (float)RAND_MAX) * 4.f - 2.f);
       CK(hipMemcpy(qkv, h.data(), h.size() * 2, hipMemcpyHostToDevice));
     }
-    CK(hipFuncSetAttribute((const void*)attn64_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_STREAM_SMEM));
+    CK(hipFuncSetAttribute((const void*)attn64_stream_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_STREAM_SMEM));
+    CK(hipFuncSetAttribute((const void*)attn64_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_STREAM_SMEM));
+    uint8_t* o8; unsigned int* sat;
+    CK(hipMalloc(&o8, max_rows * dim)); CK(hipMalloc(&sat, 4)); CK(hipMemset(sat, 0, 4));
     constexpr int psmem = 2 * 2 * 7 * 32 * 128 + 7 * 4096, fsmem9 = 9 * 32 * 256 + 4 * 4096;
     CK(hipFuncSetAttribute((const void*)attn64_persist_kernel<7, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, psmem));
     CK(hipFuncSetAttribute((const void*)attn_fwd_kernel<64, 9, false>, hipFuncAttributeMaxDynamicSharedMemorySize, fsmem9));
@@ -239,8 +243,12 @@ int main(int argc, char** argv) {
         CK(hipEventRecord(a));
         if (which == 0) {
           const int qblocks = (tokens + 32 * ATTN_STREAM_QW - 1) / (32 * ATTN_STREAM_QW);
-          hipLaunchKernelGGL(attn64_stream_kernel, dim3(items * qblocks), dim3(64 * (ATTN_STREAM_QW + 1)), ATTN_STREAM_SMEM, 0, qkv, ld, o, dim,
-                             tokens, dim, heads, qblocks, 0.125f, rm);
+          hipLaunchKernelGGL(attn64_stream_kernel<false>, dim3(items * qblocks), dim3(64 * (ATTN_STREAM_QW + 1)), ATTN_STREAM_SMEM, 0, qkv, ld, o, dim,
+                             tokens, dim, heads, qblocks, 0.125f, rm, (uint8_t*)nullptr, 0, (unsigned int*)nullptr, 0.f);
+        } else if (which == 3) {
+          const int qblocks = (tokens + 32 * ATTN_STREAM_QW - 1) / (32 * ATTN_STREAM_QW);
+          hipLaunchKernelGGL(attn64_stream_kernel<true>, dim3(items * qblocks), dim3(64 * (ATTN_STREAM_QW + 1)), ATTN_STREAM_SMEM, 0, qkv, ld, (bf16*)nullptr,
+                             dim, tokens, dim, heads, qblocks, 0.125f, rm, o8, dim, sat, ATTN_OUT8_SCALE);
         } else if (which == 1) {
           hipLaunchKernelGGL((attn64_persist_kernel<7, 1>), dim3(std::min(items, nCU)), dim3(512), psmem, 0, qkv, ld, o, dim, tokens, dim, heads, items,
                              0.125f, rm, 0, 0, (uint8_t*)nullptr, 0, (unsigned int*)nullptr, ATTN_OUT8_SCALE);
@@ -261,6 +269,7 @@ int main(int argc, char** argv) {
     time("resident persist<7,LIVE>", 197, 1);
     time("resident one-item<64,9>", 257, 2);
     for (int t : {197, 257, 577, 785, 1025}) time("stream", t, 0);
+    for (int t : {577, 1025}) { time("stream", t, 0); time("stream e4m3", t, 3); }      // back to back: the two output forms
     return 0;
   }
   hipDeviceProp_t pr; CK(hipGetDeviceProperties(&pr, 0));

@@ -26,6 +26,7 @@ SYMBOLS = [
     "ssp2_fp8_calibrate_begin", "ssp2_fp8_calibrate_end", "ssp2_fp8_attn_scale", "ssp2_fp8_set_attn_scale",
     "ssp2_create_opts", "ssp2_attention_stream_bf16", "ssp2_create_ext", "ssp2_attention_prefix_bf16",
     "ssp2_set_layer_scale", "ssp2_linear_ls_bf16", "ssp2_linear_ls_e4m3", "ssp2_linear_bf16_ex",
+    "ssp2_attention_stream_e4m3",
 ]
 
 T_KINDS = ["patch_w", "patch_b", "cls", "pos", "ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b",
@@ -34,7 +35,10 @@ T_KINDS = ["patch_w", "patch_b", "cls", "pos", "ln1_g", "ln1_b", "qkv_w", "qkv_b
 SCORE_SITE = {"none": 0, "pre_gelu": 1, "post_gelu": 2}
 SCORE_CHAIN = {"fp32": 0, "bf16_ref": 1}
 OPTIONS = {"zigzag": 0, "attn_persist": 1, "ln_fusion": 2, "big_tiles": 3, "fc1_big_tiles": 4, "group256": 5, "patch_lds": 6, "attn_stagger": 7, "fp8_proj": 8, "big_tile_min_rows": 9, "nt_stores": 10, "defer_resid": 11, "attn_live": 12, "attn_stream": 13}   # SSP2_OPT_*
-OPT_COUNT = 14                                          # SSP2_OPT_COUNT
+OPT_COUNT = 14                                          # SSP2_OPT_COUNT: the length of ssp2_create_opts' opt[] array
+# extended options (SSP2_OPT_COUNT <= index < SSP2_OPT_END): ssp2_set_option / ssp2_get_option only, no entry of the create-time array
+EXT_OPTIONS = {"stream_fp8": 14}
+OPT_END = 15                                            # SSP2_OPT_END
 ATTN_STREAM_MAX_TOKENS = 8192                           # SSP2_ATTN_STREAM_MAX_TOKENS
 K_CLASS = {"gemm_fc1": 0, "gemm_fc2": 1, "gemm_qkv": 2, "gemm_proj": 3, "gemm_patch": 4, "gemm_head": 5,
            "attn": 6, "ln": 7, "score_finish": 8, "act_l2": 9, "other": 10}
@@ -238,6 +242,7 @@ def load(build_if_missing: bool = True, variant: Optional[str] = None) -> C.CDLL
     lib.ssp2_quantise_rows_e4m3.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp]
     lib.ssp2_attention_bf16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, C.c_float, vp, i32, i32, i32]
     lib.ssp2_attention_stream_bf16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32]
+    lib.ssp2_attention_stream_e4m3.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, C.c_float, vp]
     lib.ssp2_attention_prefix_bf16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32]
     lib.ssp2_layernorm.argtypes = [vp, vp, C.c_size_t, i32, i32, vp, vp, C.c_float, i32, i32, vp, i32, vp, vp, i32]
     lib.ssp2_embed.argtypes = [vp, vp, i32, vp, i32]

@@ -9,7 +9,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import K_CLASS, OPTIONS, SCORE_CHAIN, SCORE_SITE, T_KINDS, Ssp2Error, VitDesc, VitExt, check
+from ._lib import EXT_OPTIONS, K_CLASS, OPTIONS, SCORE_CHAIN, SCORE_SITE, T_KINDS, Ssp2Error, VitDesc, VitExt, check
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -31,12 +31,15 @@ class VitEngine:
 
     def __init__(self, weights: Optional[Dict], device: str | torch.device = "cuda:0", max_images: int = 64, *,
                  precision: str = "bf16", lib_variant: Optional[str] = None, attn_stream: Optional[int] = None,
-                 _twin_of: Optional["VitEngine"] = None, _d_int: Optional[Sequence[int]] = None):
+                 stream_fp8: Optional[bool] = None, _twin_of: Optional["VitEngine"] = None, _d_int: Optional[Sequence[int]] = None):
         """`lib_variant`: a named build of the library instead of the product one — "lab" carries the opt-in kernel forms the product
         does not instantiate (options ln_fusion / defer_resid / group256; ssp2vit/_lib.py VARIANT_FLAGS).
         `attn_stream`: SSP2_OPT_ATTN_STREAM in force when the engine is created (None: the environment's SSP2_ATTN_STREAM, default 0).
         0 = resident attention kernels only (d_h = 64 up to 288 tokens); 1 = longer d_h = 64 sequences (384-pixel /16: 577 tokens,
         224-pixel /8: 785) on the key-streaming kernel; 2 = every d_h = 64 attention streams (cross-checks).  A twin inherits it.
+        `stream_fp8`: SSP2_OPT_STREAM_FP8, set before the precision is (None: the environment's SSP2_STREAM_FP8, default off).  True lets
+        an engine on the key-streaming attention run precision="fp8": its attention writes e4m3 for the e4m3 out-projection, as the
+        persistent kernels do (set_option("fp8_proj", 0) keeps both on bf16).  A twin inherits it.
         Token layout: `weights["prefix_tokens"]` (default 1; 2 = CLS + distillation token, DeiT) and a distillation head when the
         dictionary has `head_dist_w` (logits = mean of the CLS and DIST heads) go to ssp2_create_ext; a twin inherits them too.
         LayerScale: `weights["ls1.i"]` / `weights["ls2.i"]` (fp32 [dim]: timm Block.ls1 / ls2 gamma) scale block i's attention / MLP
@@ -46,10 +49,13 @@ class VitEngine:
             raise ValueError(f"precision must be 'bf16' or 'fp8', got {precision!r}")
         if attn_stream is not None and (isinstance(attn_stream, bool) or attn_stream not in (0, 1, 2)):
             raise ValueError(f"attn_stream must be None, 0, 1 or 2, got {attn_stream!r}")
+        if stream_fp8 is not None and not isinstance(stream_fp8, bool):
+            raise ValueError(f"stream_fp8 must be None, False or True, got {stream_fp8!r}")
         self.precision = precision
         if _twin_of is not None:          # same architecture, other FFN widths, weights cloned on the device
             src = _twin_of
             attn_stream = src.attn_stream
+            stream_fp8 = bool(src.stream_fp8)
             weights = dict(depth=src.depth, dim=src.dim, classes=src.classes, img=src.img, patch=src.patch, heads=src.heads,
                            eps=src.eps, prefix_tokens=src.prefix_tokens, dist_head=src.dist_head, _layer_scale=src.layer_scale,
                            **{f"fc1_w.{i}": torch.empty(int(d), 0) for i, d in enumerate(_d_int)})
@@ -91,6 +97,9 @@ class VitEngine:
             self.h = h
             self.tokens = self.lib.ssp2_tokens(self.h)
             self.attn_stream = self.get_option("attn_stream")
+            if stream_fp8 is not None:
+                self.set_option("stream_fp8", int(stream_fp8))
+            self.stream_fp8 = self.get_option("stream_fp8")
             if _twin_of is None:
                 self._load(weights)
                 if precision == "fp8":
@@ -235,11 +244,18 @@ class VitEngine:
 
     def set_option(self, name: str, value: int) -> None:
         """Run-time switch of this engine (include/ssp2vit.h SSP2_OPT_*: "zigzag", "attn_persist", "ln_fusion", "big_tiles",
-        "fc1_big_tiles", "group256").  None of them changes a result bit; they exist for the tests and A/B scripts that prove it."""
-        self._check(self.lib.ssp2_set_option(self.h, OPTIONS[name], int(value)))
+        "fc1_big_tiles", "group256", ...; and the extended ones of _lib.EXT_OPTIONS: "stream_fp8").  None of them changes a result
+        bit of a bf16 engine; they exist for the tests and A/B scripts that prove it."""
+        self._check(self.lib.ssp2_set_option(self.h, self._option_index(name), int(value)))
+        if name == "stream_fp8":
+            self.stream_fp8 = int(value)
+
+    @staticmethod
+    def _option_index(name: str) -> int:
+        return OPTIONS[name] if name in OPTIONS else EXT_OPTIONS[name]
 
     def get_option(self, name: str) -> int:
-        v = self.lib.ssp2_get_option(self.h, OPTIONS[name])
+        v = self.lib.ssp2_get_option(self.h, self._option_index(name))
         if v < 0:
             self._check(v)
         return int(v)
@@ -688,10 +704,31 @@ class VitEngine:
         return out8 if out8 is not None else out
 
     def attention_stream(self, qkv: torch.Tensor, n: int, tokens: int, heads: int, d_h: int, *, group: int = 0,
-                         out: Optional[torch.Tensor] = None, q_cls: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The key-streaming attention on its own (ssp2_attention_stream_bf16): the layouts of `attention`, d_h = 64, 1..8192 tokens,
-        bf16 output only."""
+                         out: Optional[torch.Tensor] = None, q_cls: Optional[torch.Tensor] = None, out8: Optional[torch.Tensor] = None,
+                         out8_scale: float = 16.0, sat: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The key-streaming attention on its own (ssp2_attention_stream_bf16): the layouts of `attention`, d_h = 64, 1..8192 tokens.
+        With out8 (uint8 [>= rows, ldo8], ldo8 a multiple of 16; full form only) the fp8 mode's e4m3(o * out8_scale) bytes instead of
+        the bf16 output (ssp2_attention_stream_e4m3), out8_scale a power of two, clipping waves counted into sat (int32 [1])."""
         dim = heads * d_h
+        if out8 is not None:
+            if out is not None or q_cls is not None:
+                raise ValueError("out8 replaces the bf16 output of the full form: no out, no q_cls")
+            if qkv.device.type != "cuda" or qkv.dim() != 2 or qkv.dtype != torch.bfloat16 or qkv.stride(1) != 1:
+                raise ValueError("qkv must be a row-major 2-D bf16 device tensor")
+            if out8.device.type != "cuda" or out8.dim() != 2 or out8.dtype != torch.uint8 or out8.stride(1) != 1 or out8.stride(0) < out8.shape[1]:
+                raise ValueError("out8 must be a row-major 2-D uint8 device tensor")
+            if sat is not None and (sat.device.type != "cuda" or sat.dtype != torch.int32 or sat.numel() < 1):
+                raise ValueError("sat must be an int32 device tensor")
+            need = ssp2_rows(n, tokens, group)
+            if qkv.shape[1] != 3 * dim or qkv.stride(0) != 3 * dim or qkv.shape[0] < need:
+                raise ValueError(f"qkv [{tuple(qkv.shape)}] must be [>= {need}, {3 * dim}], densely packed (the kernels' row stride)")
+            if out8.shape[0] < need or out8.shape[1] < dim:
+                raise ValueError(f"output [{tuple(out8.shape)}] smaller than [{need}, {dim}]")
+            self._check(self.lib.ssp2_attention_stream_e4m3(C.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream), _ptr(qkv), n, tokens,
+                                                            heads, d_h, group, _ptr(out8), out8.stride(0), float(out8_scale), _ptr(sat)))
+            return out8
+        if sat is not None:
+            raise ValueError("sat counts the clipping waves of the e4m3 output: it needs out8")
         for name, t in (("qkv", qkv), ("out", out), ("q_cls", q_cls)):
             if t is not None and (t.device.type != "cuda" or t.dim() != 2 or t.dtype != torch.bfloat16 or t.stride(1) != 1 or t.stride(0) < t.shape[1]):
                 raise ValueError(f"{name} must be a row-major 2-D bf16 device tensor")

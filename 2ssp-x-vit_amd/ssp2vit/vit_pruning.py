@@ -120,6 +120,9 @@ def _fingerprint(model) -> Tuple:
 DEFAULT_PRECISION = os.environ.get("SSP2_PRECISION", "bf16")
 # SSP2_OPT_ATTN_STREAM of the engines built for live modules: None = the environment (SSP2_ATTN_STREAM); the CLI's --long-sequences sets 1
 DEFAULT_ATTN_STREAM: Optional[int] = None
+# SSP2_OPT_STREAM_FP8 of those engines (fp8 on the key-streaming attention): None = the environment (SSP2_STREAM_FP8); the CLI's
+# --long-sequences --precision fp8 sets True
+DEFAULT_STREAM_FP8: Optional[bool] = None
 _FP8_SCALES: Dict[int, List[float]] = {}          # id(model) -> calibrated attention hand-off scales (calibrate_fp8), re-applied when an engine is rebuilt
 
 
@@ -137,14 +140,30 @@ def attn_stream_setting(attn_stream: Optional[int] = None) -> int:
     return int(attn_stream)
 
 
-def engine_for(model, device="cuda", max_images: int = 64, precision: Optional[str] = None, attn_stream: Optional[int] = None):
-    """Build (or reuse) the HIP engine holding `model`'s current weights.  Raises without a GPU.  `attn_stream`: see
-    VitEngine (None: attn_stream_setting()); the cache and the pool are keyed on it as well as on the geometry."""
+def stream_fp8_setting(stream_fp8: Optional[bool] = None) -> bool:
+    """The SSP2_OPT_STREAM_FP8 an engine built now gets: the argument, else DEFAULT_STREAM_FP8 (the CLI's --long-sequences --precision
+    fp8), else the environment's SSP2_STREAM_FP8 (what ssp2_create reads), else off."""
+    if stream_fp8 is None:
+        stream_fp8 = DEFAULT_STREAM_FP8
+    if stream_fp8 is None:
+        try:
+            stream_fp8 = int(os.environ.get("SSP2_STREAM_FP8", "") or 0) != 0
+        except ValueError:
+            stream_fp8 = False
+    return bool(stream_fp8)
+
+
+def engine_for(model, device="cuda", max_images: int = 64, precision: Optional[str] = None, attn_stream: Optional[int] = None,
+               stream_fp8: Optional[bool] = None):
+    """Build (or reuse) the HIP engine holding `model`'s current weights.  Raises without a GPU.  `attn_stream` / `stream_fp8`: see
+    VitEngine (None: attn_stream_setting() / stream_fp8_setting()); the cache and the pool are keyed on the former as well as on the
+    geometry, the cache on the latter too (only fp8 engines read it, and those never wait in the pool)."""
     from .engine import VitEngine
     precision = precision or DEFAULT_PRECISION
     attn_stream = attn_stream_setting(attn_stream)
+    stream_fp8 = stream_fp8_setting(stream_fp8)
     key = id(model)
-    fp = _fingerprint(model) + (precision, attn_stream) + _weights.token_layout(model) + (_weights.has_layer_scale(model),)
+    fp = _fingerprint(model) + (precision, attn_stream, stream_fp8) + _weights.token_layout(model) + (_weights.has_layer_scale(model),)
     hit = _ENGINES.get(key)
     if hit is not None and hit[0] == fp and hit[1].max_images >= max_images:
         return hit[1]
@@ -161,7 +180,8 @@ def engine_for(model, device="cuda", max_images: int = 64, precision: Optional[s
     while len(_POOL) > ENGINE_POOL_MAX:
         _POOL.pop(0).close()
     if eng is None:
-        eng = VitEngine(flat, device=dev, max_images=max(int(max_images), 1), precision=precision, attn_stream=attn_stream)
+        eng = VitEngine(flat, device=dev, max_images=max(int(max_images), 1), precision=precision, attn_stream=attn_stream,
+                        stream_fp8=stream_fp8)
     eng.layout = _weights.detect_layout(model)
     if precision == "fp8" and key in _FP8_SCALES and len(_FP8_SCALES[key]) == eng.depth:
         for l, sc in enumerate(_FP8_SCALES[key]):

@@ -132,10 +132,19 @@ int ssp2_set_cu_limit(ssp2_handle h, int n_cu);
  *                                                   over 288 tokens stream, shorter ones keep the resident kernels bit for bit; 2 = every
  *                                                   d_h = 64 attention streams (cross-checks; within tolerance of the resident kernels, not
  *                                                   bit-identical).  An engine whose geometry needs it refuses 0 (SSP2_ESTATE); a streaming
- *                                                   engine refuses fp8 (ssp2_set_precision: SSP2_ESTATE) */
+ *                                                   engine refuses fp8 (ssp2_set_precision: SSP2_ESTATE) unless SSP2_OPT_STREAM_FP8
+ *   SSP2_OPT_STREAM_FP8     0  SSP2_STREAM_FP8      0 / 1: a streaming engine accepts fp8 (ssp2_set_precision, SSP2_OPT_ATTN_STREAM on an fp8 engine):
+ *                                                   QKV, fc1 and fc2 run on e4m3 operands and, with SSP2_OPT_FP8_PROJ, the key-streaming kernel
+ *                                                   writes e4m3(o * s_l) for an e4m3 out-projection, as the persistent kernels do.  Changes
+ *                                                   nothing while 0 and nothing on a bf16 engine.  An EXTENDED option: ssp2_set_option /
+ *                                                   ssp2_get_option and the environment only — the opt[] array of ssp2_create_opts keeps its
+ *                                                   SSP2_OPT_COUNT entries (a caller built against an earlier header passes that many), and
+ *                                                   the option is read no earlier than ssp2_set_precision */
 enum { SSP2_OPT_ZIGZAG = 0, SSP2_OPT_ATTN_PERSIST, SSP2_OPT_LN_FUSION, SSP2_OPT_BIG_TILES, SSP2_OPT_FC1_BIG_TILES, SSP2_OPT_GROUP256,
        SSP2_OPT_PATCH_LDS, SSP2_OPT_ATTN_STAGGER, SSP2_OPT_FP8_PROJ, SSP2_OPT_BIG_TILE_MIN_ROWS, SSP2_OPT_NT_STORES,
        SSP2_OPT_DEFER_RESID, SSP2_OPT_ATTN_LIVE, SSP2_OPT_ATTN_STREAM, SSP2_OPT_COUNT };
+/* extended options, behind the create-time table: ssp2_set_option / ssp2_get_option take [0, SSP2_OPT_END) */
+enum { SSP2_OPT_STREAM_FP8 = SSP2_OPT_COUNT, SSP2_OPT_END };
 #define SSP2_ATTN_STREAM_MAX_TOKENS 8192   /* longest sequence of the key-streaming attention */
 int ssp2_set_option(ssp2_handle h, int option, int value);
 int ssp2_get_option(ssp2_handle h, int option);                             /* >= 0, or SSP2_EINVAL */
@@ -381,6 +390,13 @@ int ssp2_attention_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int to
  * fp32.  Every argument is checked before the device is touched. */
 int ssp2_attention_stream_bf16(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
                                const uint16_t* q_cls_dev, uint16_t* out_dev, int ldo);
+/* Additive (ABI stays 7): the full key-streaming attention with the fp8 mode's output (what an fp8 engine with SSP2_OPT_STREAM_FP8
+ * launches): out8_dev receives e4m3(o * out8_scale) bytes [rows, ldo8], saturating at +-448, taken from the fp32 accumulator (no bf16
+ * rounding in between), image rows and columns [0, heads * 64) only; every wave that clipped a value adds 1 to *sat_dev (may be NULL).
+ * The checks of ssp2_attention_stream_bf16, and: out8_dev 16-byte aligned, ldo8 >= heads * 64 and a multiple of 16, out8_scale a
+ * positive power of two.  Every argument is checked before the device is touched. */
+int ssp2_attention_stream_e4m3(void* hip_stream, const uint16_t* qkv_dev, int n, int tokens, int heads, int d_h, int group,
+                               uint8_t* out8_dev, int ldo8, float out8_scale, unsigned int* sat_dev);
 /* The prefix-query attention of the evaluation tail on its own: the CLS-only form of ssp2_attention_bf16 (resident kernels; stream != 0:
  * the key-streaming kernel of ssp2_attention_stream_bf16, d_h = 64 only) for n_prefix = 1 or 2 queries per image.  q_dev bf16 holds
  * the queries prefix-major, [n_prefix][n][heads * d_h] densely packed; out_dev bf16 [n_prefix][n][ldo] receives them in the same order
