@@ -412,10 +412,27 @@ class VitEngine:
                                           SCORE_CHAIN[score_chain], int(score_group), ns, _ptr(batch_scores if site else None), self.score_ld))
         return batch_scores if site else None
 
+    def _logits_pred(self, n: int, want_logits: bool, want_pred: bool, logits: Optional[torch.Tensor], pred: Optional[torch.Tensor]):
+        """The head's outputs: the caller's own buffers (logits f32 [>= n, classes] densely packed, pred int32 [>= n]: the kernels write
+        n rows at a row stride of `classes`) or fresh ones when asked for."""
+        if logits is not None and (logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[0] < n
+                                   or logits.shape[1] != self.classes or not logits.is_contiguous()):
+            raise ValueError(f"logits must be a contiguous f32 device tensor of [>= {n}, {self.classes}]")
+        if pred is not None and (pred.device != self.device or pred.dtype != torch.int32 or pred.dim() != 1 or pred.numel() < n
+                                 or not pred.is_contiguous()):
+            raise ValueError(f"pred must be a contiguous int32 device tensor of >= {n} entries")
+        if logits is None and want_logits:
+            logits = torch.empty(n, self.classes, dtype=torch.float32, device=self.device)
+        if pred is None and want_pred:
+            pred = torch.empty(n, dtype=torch.int32, device=self.device)
+        return logits, pred
+
     def head(self, x: torch.Tensor, n: int, labels: Optional[torch.Tensor] = None,
-             correct: Optional[torch.Tensor] = None, want_logits: bool = False, want_pred: bool = False, group: int = 0):
-        logits = torch.empty(n, self.classes, dtype=torch.float32, device=self.device) if want_logits else None
-        pred = torch.empty(n, dtype=torch.int32, device=self.device) if want_pred else None
+             correct: Optional[torch.Tensor] = None, want_logits: bool = False, want_pred: bool = False, group: int = 0, *,
+             logits: Optional[torch.Tensor] = None, pred: Optional[torch.Tensor] = None):
+        """Final norm + classifier (+ top-1) on the prefix rows of x.  `logits` / `pred`: buffers of the caller's to write into (rows
+        behind n are left alone); returned as given."""
+        logits, pred = self._logits_pred(n, want_logits, want_pred, logits, pred)
         if labels is not None:
             labels = labels.to(self.device, torch.int64, non_blocking=True).contiguous()
             if correct is None:
@@ -427,15 +444,15 @@ class VitEngine:
 
     def tail(self, x: torch.Tensor, n: int, attn_skip: Optional[Sequence[int]] = None,
              labels: Optional[torch.Tensor] = None, correct: Optional[torch.Tensor] = None, want_logits: bool = False,
-             want_pred: bool = False, slots: int = 1, group: int = 0):
+             want_pred: bool = False, slots: int = 1, group: int = 0, *, logits: Optional[torch.Tensor] = None,
+             pred: Optional[torch.Tensor] = None):
         """Last encoder block + head on the CLS rows only (x must hold the residual stream ENTERING the last block;
         it is not modified).  Same results, bit for bit, as layers(x, depth-1, depth) + head(x).
         `slots` > 1: x holds that many streams of n images side by side (ssp2_tail_slots); labels [n] are shared, `correct`
         must have `slots` entries (slot s is counted in correct[s]), logits / pred cover slots * n images.
-        `group` > 0: the streams are in the slab layout of `rows(slots * n, group)` (ssp2_tail_group)."""
-        tot = n * int(slots)
-        logits = torch.empty(tot, self.classes, dtype=torch.float32, device=self.device) if want_logits else None
-        pred = torch.empty(tot, dtype=torch.int32, device=self.device) if want_pred else None
+        `group` > 0: the streams are in the slab layout of `rows(slots * n, group)` (ssp2_tail_group).
+        `logits` / `pred`: buffers of the caller's, as in `head`."""
+        logits, pred = self._logits_pred(n * int(slots), want_logits, want_pred, logits, pred)
         if labels is not None:
             labels = labels.to(self.device, torch.int64, non_blocking=True).contiguous()
             if correct is None:
