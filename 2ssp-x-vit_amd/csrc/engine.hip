@@ -608,6 +608,16 @@ static int launch_attn(ssp2_engine* e, int n, RowMap rm, bool cls_only = false, 
 
 static int act_l2_impl(void* stream, const void* act, int dtype, int n, RowMap rm, int d, int ld, int chain, int group,
                        float* norms_ws, float* out, size_t out_stride);
+// The fused score finish: the fc1 epilogue's slab -> per-sample norms -> per-group sums.  The two launches the forward's hook issues
+// (score_finish) and the ones ssp2_score_finish issues: one function, so that the entry is the forward's launch and not a copy of it.
+static int score_finish_fused(hipStream_t s, const float* slab, int n, RowMap rm, int grp, int ld, int chain, float* norms, float* out,
+                              size_t out_stride) {
+  const int n_groups = (n + grp - 1) / grp;
+  hipLaunchKernelGGL(score_norms_from_slab_kernel, dim3((ld + 255) / 256, n), dim3(256), 0, s, slab, norms, n, rm, ld, chain);
+  hipLaunchKernelGGL(score_colsum_kernel, dim3((ld + 255) / 256, n_groups), dim3(256), 0, s, norms, out, out_stride, n, grp, ld, chain);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 // the unfused scoring path (models with < 128 tokens) reads the bf16 activation back: it stays on the bf16 kernels
 static inline bool fused_ok_for_fp8(int score_site, int tokens) { return score_site == 0 || tokens >= GEMM_BM; }
 
@@ -1224,7 +1234,7 @@ struct LayersCall {
   int score_site, score_chain; bool scores_only; float* batch_scores; int score_ld;
   bool fused;                                 // the fc1 epilogue scores (a 128-row tile then spans at most two samples); else the standalone L2 kernel
   bool split; int ns, M0;                     // hook on the leading ns images only: fc1 runs as rows [0, M0) scored + rows [M0, M) plain
-  int grp, n_groups; size_t group_stride;     // score groups of the hooked images
+  int grp; size_t group_stride;               // score groups of the hooked images
   // fp8 mode: the three large projections of a launch with >= 4096 rows run on e4m3 operands (LayerNorm and the fc1
   // epilogue write the activation as e4m3 bytes); attention, the out-projection and small launches stay bf16
   bool f8, f8_fc1;
@@ -1251,7 +1261,7 @@ static int attn_half(ssp2_engine* e, LayersCall& c, int l) {
   if ((rc = launch_attn(e, c.n, c.rm, false, f8_proj ? e->obuf8 : nullptr, L.o8_scale))) return rc;
   if (c.f8 && e->fp8_calibrating && e->attn_amax) {
     ProfScope ps(e, SSP2_K_OTHER);
-    hipLaunchKernelGGL(absmax_bf16_kernel, dim3(1024), dim3(256), 0, e->stream, e->obuf, (long)M, D, D, e->attn_amax + l);
+    hipLaunchKernelGGL(absmax_bf16_kernel, dim3(1024), dim3(256), 0, e->stream, e->obuf, (long)M, D, D, e->attn_amax + l, c.rm, c.n);
     HIPCHK(hipGetLastError());
   }
   GemmArgs p = bind(L.proj, f8_proj ? act_e4m3(e->obuf8, e->ld8_dim, nullptr, 1.0f / L.o8_scale) : act_bf16(e->obuf, D), M, D);
@@ -1272,12 +1282,7 @@ static int score_finish(ssp2_engine* e, const LayersCall& c, int l) {
   float* row = c.batch_scores + (size_t)l * c.score_ld;
   if (c.fused) {
     ProfScope ps(e, SSP2_K_SCORE_FINISH);
-    hipLaunchKernelGGL(score_norms_from_slab_kernel, dim3((L.ld_int + 255) / 256, c.ns), dim3(256), 0, e->stream,
-                       e->slab, e->norms, c.ns, c.rm, L.ld_int, c.score_chain);
-    hipLaunchKernelGGL(score_colsum_kernel, dim3((L.ld_int + 255) / 256, c.n_groups), dim3(256), 0, e->stream, e->norms, row,
-                       c.group_stride, c.ns, c.grp, L.ld_int, c.score_chain);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return score_finish_fused(e->stream, e->slab, c.ns, c.rm, c.grp, L.ld_int, c.score_chain, e->norms, row, c.group_stride);
   }
   const bf16* seen = (c.score_site == SSP2_SCORE_PRE_GELU) ? e->prebuf : e->actbuf;
   ProfScope ps(e, SSP2_K_ACT_L2);
@@ -1320,7 +1325,7 @@ static int mlp_half(ssp2_engine* e, LayersCall& c, int l) {
   if (rc) return rc;
   if (f8 && e->fp8_calibrating && e->act8_top) {       // calibration pass: how much of the GELU output did the saturating e4m3 cast put on its top code?
     ProfScope ps(e, SSP2_K_OTHER);
-    hipLaunchKernelGGL(e4m3_top_code_count_kernel, dim3(1024), dim3(256), 0, e->stream, e->act8, (long)M, ceil_to(L.d_int, 16), ld8_int, e->act8_top);
+    hipLaunchKernelGGL(e4m3_top_code_count_kernel, dim3(1024), dim3(256), 0, e->stream, e->act8, (long)M, ceil_to(L.d_int, 16), ld8_int, e->act8_top, c.rm, c.n);
     HIPCHK(hipGetLastError());
   }
   if (c.score_site && (rc = score_finish(e, c, l))) return rc;
@@ -1372,7 +1377,6 @@ int ssp2_layers_prefix(ssp2_handle e, const float* x_in, float* x, int n, int l_
   c.ns = score_site ? score_images : n;                                            // images that are hooked
   c.M0 = c.split ? (score_images / c.rm.group) * c.rm.mpad : c.M;                  // rows of the scored prefix: whole padded slabs
   c.grp = (score_group <= 0 || score_group > n) ? n : score_group;
-  c.n_groups = (c.ns + c.grp - 1) / c.grp;
   c.group_stride = (size_t)e->d.depth * score_ld;
   c.fused = score_site && e->tokens >= GEMM_BM;
   c.f8 = e->fp8 && c.M >= big_tile_min_rows(e);
@@ -1668,6 +1672,56 @@ int ssp2_prune_ffn_into(ssp2_handle dst, ssp2_handle src, int layer, const int32
 int ssp2_act_l2_accum(void* stream, const void* act, int dtype, int n, int tokens, int d, int ld, int chain, int group,
                       float* norms_ws, float* out, size_t out_stride) {
   return act_l2_impl(stream, act, dtype, n, RowMap{tokens, 0, 0}, d, ld, chain, group, norms_ws, out, out_stride);
+}
+
+int ssp2_score_finish(void* hip_stream, const float* slab_dev, int n, int tokens, int group, int ld, int chain, float* norms_ws_dev,
+                      float* out_dev, size_t out_stride) {
+  if (!slab_dev || !norms_ws_dev || !out_dev) return fail(SSP2_EINVAL, "score_finish: null device pointer");
+  if (n <= 0 || group < 0) return fail(SSP2_EINVAL, "score_finish: n=%d group=%d", n, group);
+  if (tokens < GEMM_BM) return fail(SSP2_EINVAL, "score_finish: tokens=%d (the fused hook needs >= %d: a 128-row tile spans at most two samples)", tokens, GEMM_BM);
+  if (ld < 1) return fail(SSP2_EINVAL, "score_finish: ld=%d", ld);
+  if (out_stride < (size_t)ld) return fail(SSP2_EINVAL, "score_finish: out_stride=%zu < ld=%d", out_stride, ld);
+  if (chain != SSP2_CHAIN_FP32 && chain != SSP2_CHAIN_BF16_REF) return fail(SSP2_EINVAL, "score_finish: chain=%d", chain);
+  const RowMap rm = make_rowmap(tokens, n, group);
+  if (total_rows(rm, n) > 0x7fffffffL) return fail(SSP2_EINVAL, "score_finish: too many rows");
+  const int grp = (group <= 0 || group > n) ? n : group;
+  return score_finish_fused((hipStream_t)hip_stream, slab_dev, n, rm, grp, ld, chain, norms_ws_dev, out_dev, out_stride);
+}
+
+int ssp2_peek_tensor(ssp2_handle e, int kind, int layer, int image, void* host, size_t bytes) {
+  if (!e || !host) return fail(SSP2_EINVAL, "peek_tensor: null argument");
+  IngestTarget t;
+  if (int rc = resolve_tensor(e, kind, layer, &t)) return rc;
+  const Mat* m = t.m;
+  const void* src = nullptr;
+  size_t want = 0;
+  int32_t shape[5];
+  switch (image) {
+    case SSP2_PEEK_SHAPE:
+      if (t.type == 0) { shape[0] = m->rows; shape[1] = m->cols; shape[2] = m->rows_pad; shape[3] = m->ld; shape[4] = m->w8 ? m->ld8 : 0; }
+      else if (t.type == 1) { shape[0] = m->rows; shape[1] = 1; shape[2] = m->rows_pad; shape[3] = 1; shape[4] = 0; }
+      else { shape[0] = shape[2] = (int32_t)t.expect; shape[1] = shape[3] = 1; shape[4] = 0; }
+      if (bytes != sizeof shape) return fail(SSP2_EINVAL, "peek_tensor: the shape is %zu bytes, got %zu", sizeof shape, bytes);
+      memcpy(host, shape, sizeof shape);
+      return 0;
+    case SSP2_PEEK_IMAGE:
+      if (t.type == 0) { src = m->w; want = (size_t)m->rows_pad * m->ld * 2; }
+      else if (t.type == 1) { src = m->b; want = (size_t)m->rows_pad * 4; }
+      else { src = t.dst; want = t.expect * 4; }
+      break;
+    case SSP2_PEEK_E4M3:
+    case SSP2_PEEK_SCALE:
+      if (t.type != 0) return fail(SSP2_EINVAL, "peek_tensor: kind %d is no matrix: it has no e4m3 image", kind);
+      if (!m->w8 || !m->wscale) return fail(SSP2_ESTATE, "peek_tensor: kind %d, layer %d has no e4m3 image (ssp2_set_precision quantises QKV, proj, fc1 and fc2)", kind, layer);
+      if (image == SSP2_PEEK_E4M3) { src = m->w8; want = (size_t)m->rows_pad * m->ld8; }
+      else { src = m->wscale; want = (size_t)m->rows_pad * 4; }
+      break;
+    default: return fail(SSP2_EINVAL, "peek_tensor: unknown image %d", image);
+  }
+  if (bytes != want) return fail(SSP2_EINVAL, "peek_tensor: kind %d, layer %d, image %d is %zu bytes, got %zu", kind, layer, image, want, bytes);
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(host, src, want, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 // The engine of an operator entry (ssp2_linear_*, ssp2_attention_*, ssp2_layernorm): a stack object that owns nothing, on the caller's
@@ -2085,6 +2139,8 @@ static int act_l2_impl(void* stream, const void* act, int dtype, int n, RowMap r
   const int tokens = rm.tokens;
   if (!act || !norms_ws || !out) return fail(SSP2_EINVAL, "null device pointer");
   if (n <= 0 || tokens <= 0 || d <= 0 || ld < d || (ld % 8)) return fail(SSP2_EINVAL, "bad shape n=%d tokens=%d d=%d ld=%d (ld multiple of 8, >= d)", n, tokens, d, ld);
+  // every column j < ld of a group's row is written: a smaller stride would let one group's block write into the next group's row
+  if (out_stride < (size_t)ld) return fail(SSP2_EINVAL, "out_stride=%zu < ld=%d", out_stride, ld);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((ld + 511) / 512, n, 2), blk(256);       // z = token half (see act_l2_norms_kernel)
   // non-temporal loads: the activation is read once (5.28 -> 5.78 TB/s on the 512-image tensor, profiles/r02_d_act_l2_nt_ab.txt)

@@ -480,15 +480,26 @@ __global__ __launch_bounds__(256) void quant_rows_e4m3_kernel(const bf16* __rest
   if (lane == 0) scale[row] = sc;
 }
 
+// fp8 calibration: does row r of a token matrix in the layout `rm` (common.hip.h RowMap) belong to one of its n images?  The slab layout
+// pads every slab to a multiple of 128 rows; those rows, and rows behind the last image, are no image's.
+__device__ __forceinline__ bool row_is_image(const RowMap rm, int n, long r) {
+  if (rm.group <= 0) return r < (long)n * rm.tokens;
+  const long slab = r / rm.mpad, off = r - slab * rm.mpad;
+  return off < (long)rm.group * rm.tokens && slab * rm.group + off / rm.tokens < n;
+}
+
 // fp8 calibration (ssp2_fp8_calibrate_*): how many e4m3 bytes of the fc1 -> fc2 hand-off [rows, cols] (leading dimension ld bytes) sit ON the
 // top code (+-448, 0x7e / 0xfe) — what the saturating cast of the GELU output writes for every value at or beyond the e4m3 range.  The fc1
 // epilogue cannot count them itself (no register left: 253 VGPRs); a calibration pass can afford one more read of the activation.
-__global__ void e4m3_top_code_count_kernel(const uint8_t* __restrict__ a, long rows, int cols, int ld, unsigned long long* __restrict__ count) {
+// Only rows of the launch's n images count (row_is_image): the slab layout's pad rows carry fc1 of the LayerNorm of pad rows.
+__global__ void e4m3_top_code_count_kernel(const uint8_t* __restrict__ a, long rows, int cols, int ld, unsigned long long* __restrict__ count,
+                                           RowMap rm, int n) {
   unsigned int c = 0;
   const int c16 = cols / 16;
   const long n16 = rows * c16;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (long)gridDim.x * blockDim.x) {
     const long r = i / c16; const int k = (int)(i - r * c16);
+    if (!row_is_image(rm, n, r)) continue;
     const i32x4 v = *(const i32x4*)(a + r * ld + k * 16);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -504,11 +515,14 @@ __global__ void e4m3_top_code_count_kernel(const uint8_t* __restrict__ a, long r
 // ------------------------------------------------------------------------------------------------
 // fp8 calibration (ssp2_fp8_calibrate_*): largest |value| of a bf16 matrix [rows, cols] (leading dimension ld) -> atomicMax on the bits of
 // a non-negative float (*amax_bits; non-negative floats order as unsigned integers).
-__global__ void absmax_bf16_kernel(const bf16* __restrict__ a, long rows, int cols, int ld, unsigned int* __restrict__ amax_bits) {
+// Only rows of the launch's n images count (row_is_image): the attention never writes the slab layout's pad rows, so they hold whatever an
+// earlier call left there.
+__global__ void absmax_bf16_kernel(const bf16* __restrict__ a, long rows, int cols, int ld, unsigned int* __restrict__ amax_bits, RowMap rm, int n) {
   float m = 0.f;
   const long n8 = rows * (cols / 8);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
     const long r = i / (cols / 8); const int c = (int)(i - r * (cols / 8));
+    if (!row_is_image(rm, n, r)) continue;
     const bf16x8 v = *(const bf16x8*)(a + r * ld + c * 8);
 #pragma unroll
     for (int k = 0; k < 8; ++k) m = fmaxf(m, fabsf((float)v[k]));

@@ -26,7 +26,7 @@ SYMBOLS = [
     "ssp2_fp8_calibrate_begin", "ssp2_fp8_calibrate_end", "ssp2_fp8_attn_scale", "ssp2_fp8_set_attn_scale",
     "ssp2_create_opts", "ssp2_attention_stream_bf16", "ssp2_create_ext", "ssp2_attention_prefix_bf16",
     "ssp2_set_layer_scale", "ssp2_linear_ls_bf16", "ssp2_linear_ls_e4m3", "ssp2_linear_bf16_ex",
-    "ssp2_attention_stream_e4m3",
+    "ssp2_attention_stream_e4m3", "ssp2_score_finish", "ssp2_peek_tensor",
 ]
 
 T_KINDS = ["patch_w", "patch_b", "cls", "pos", "ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b",
@@ -40,6 +40,7 @@ OPT_COUNT = 14                                          # SSP2_OPT_COUNT: the le
 EXT_OPTIONS = {"stream_fp8": 14}
 OPT_END = 15                                            # SSP2_OPT_END
 ATTN_STREAM_MAX_TOKENS = 8192                           # SSP2_ATTN_STREAM_MAX_TOKENS
+PEEK = {"shape": 0, "image": 1, "e4m3": 2, "scale": 3}   # SSP2_PEEK_*
 K_CLASS = {"gemm_fc1": 0, "gemm_fc2": 1, "gemm_qkv": 2, "gemm_proj": 3, "gemm_patch": 4, "gemm_head": 5,
            "attn": 6, "ln": 7, "score_finish": 8, "act_l2": 9, "other": 10}
 
@@ -262,6 +263,8 @@ def load(build_if_missing: bool = True, variant: Optional[str] = None) -> C.CDLL
     lib.ssp2_prune_ffn_into.argtypes = [vp, vp, i32, C.POINTER(C.c_int32), i32]
     lib.ssp2_d_int.argtypes = [vp, i32]
     lib.ssp2_act_l2_accum.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, C.c_size_t]
+    lib.ssp2_score_finish.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, C.c_size_t]
+    lib.ssp2_peek_tensor.argtypes = [vp, i32, i32, i32, vp, C.c_size_t]
     lib.ssp2_profile_begin.argtypes = [vp, i32]
     lib.ssp2_profile_end.argtypes = [vp, C.POINTER(C.c_double), i64p, C.POINTER(C.c_double)]
     lib.ssp2_profile_query.argtypes = [vp, i32, C.POINTER(C.c_double), i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]

@@ -477,6 +477,55 @@ class VitEngine:
                                          n, t, d, d, SCORE_CHAIN[score_chain], 0, _ptr(ws), _ptr(out), d))
         return out
 
+    def score_finish(self, slab: torch.Tensor, n: int, tokens: int, group: int = 0, score_chain: str = "fp32", *,
+                     norms: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The forward's fused score finish on a slab of the caller's (ssp2_score_finish): slab f32 [tiles, 2, ld] -> (out f32
+        [ceil(n / group), out_stride] of which columns [0, ld) are written, norms f32 [n, ld]).  `norms` / `out`: the caller's buffers."""
+        if slab.dim() != 3 or slab.shape[1] != 2 or slab.dtype != torch.float32 or not slab.is_contiguous() or slab.device.type != "cuda":
+            raise ValueError("slab must be a contiguous f32 [tiles, 2, ld] device tensor")
+        ld = int(slab.shape[2])
+        rows = ssp2_rows(int(n), int(tokens), int(group))
+        if int(slab.shape[0]) < 2 * (-(-rows // 256)):
+            raise ValueError(f"slab holds {int(slab.shape[0])} tiles, the layout has {2 * (-(-rows // 256))}")
+        grp = n if (group <= 0 or group > n) else group
+        if norms is None:
+            norms = torch.empty(n, ld, dtype=torch.float32, device=slab.device)
+        if out is None:
+            out = torch.empty(-(-n // grp), ld, dtype=torch.float32, device=slab.device)
+        for name, t, r in (("norms", norms, n), ("out", out, -(-n // grp))):
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < r or t.shape[1] < ld or not t.is_contiguous() or t.device != slab.device:
+                raise ValueError(f"{name} must be a contiguous f32 [>= {r}, >= {ld}] tensor on the slab's device")
+        if int(norms.shape[1]) != ld:
+            raise ValueError(f"norms must be [n, {ld}] densely packed")
+        self._check(self.lib.ssp2_score_finish(C.c_void_p(torch.cuda.current_stream(slab.device).cuda_stream), _ptr(slab), int(n), int(tokens),
+                                               int(group), ld, SCORE_CHAIN[score_chain], _ptr(norms), _ptr(out), int(out.shape[1])))
+        return out, norms
+
+    def peek_shape(self, kind: str, layer: int = 0) -> Dict[str, int]:
+        """rows, cols, rows_pad, ld, ld8 of what the engine holds for tensor `kind` of block `layer` (ssp2_peek_tensor, SSP2_PEEK_SHAPE)."""
+        buf = (C.c_int32 * 5)()
+        self._check(self.lib.ssp2_peek_tensor(self.h, T_KINDS.index(kind), int(layer), _lib.PEEK["shape"], buf, 20))
+        return dict(zip(("rows", "cols", "rows_pad", "ld", "ld8"), (int(v) for v in buf)))
+
+    def peek_tensor(self, kind: str, layer: int = 0, image: str = "image") -> torch.Tensor:
+        """What the engine holds, read back to the CPU (ssp2_peek_tensor; synchronises): image "image" -> a matrix's bf16 [rows_pad, ld],
+        a bias's f32 [rows_pad], a vector's f32 [rows]; "e4m3" -> uint8 [rows_pad, ld8] and "scale" -> f32 [rows_pad] of a matrix in
+        fp8 mode."""
+        s = self.peek_shape(kind, layer)
+        is_mat = kind.endswith("_w")
+        if image == "image":
+            t = torch.empty(s["rows_pad"], s["ld"], dtype=torch.bfloat16) if is_mat else torch.empty(s["rows_pad"], dtype=torch.float32)
+        elif image == "e4m3":
+            t = torch.empty(s["rows_pad"], s["ld8"], dtype=torch.uint8) if s["ld8"] else torch.empty(1, dtype=torch.uint8)   # (none: the library says so)
+        elif image == "scale":
+            t = torch.empty(s["rows_pad"], dtype=torch.float32)
+        else:
+            raise ValueError(f"image must be 'image', 'e4m3' or 'scale', got {image!r}")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.ssp2_peek_tensor(self.h, T_KINDS.index(kind), int(layer), _lib.PEEK[image], C.c_void_p(t.data_ptr()),
+                                                  t.numel() * t.element_size()))
+        return t
+
     def linear(self, a: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], epilogue: str = "bf16",
                x: Optional[torch.Tensor] = None, kernel: str = "auto", *, gamma: Optional[torch.Tensor] = None,
                xin: Optional[torch.Tensor] = None, rev: int = 0) -> torch.Tensor:

@@ -198,7 +198,8 @@ int ssp2_set_precision(ssp2_handle h, int mode);
  *                                        was seen (2^-8 <= s_l <= 2^10; others keep 16), switches the recording off; synchronises
  *   ssp2_fp8_attn_scale(h, l)            the scale in force for block l (e.g. to store it with a checkpoint); ssp2_fp8_set_attn_scale
  *                                        sets it directly (a power of two > 0)
- * Explicit and deterministic: the scales depend only on the images handed over between begin and end, never on launch order. */
+ * Explicit and deterministic: the scales depend only on the images handed over between begin and end, never on launch order — in either
+ * row layout: the slab layout's pad rows (ssp2_rows) count neither towards max |o| nor towards SSP2_Q_FP8_FC2_TOP_CODES. */
 int ssp2_fp8_calibrate_begin(ssp2_handle h);
 int ssp2_fp8_calibrate_end(ssp2_handle h, float headroom);
 float ssp2_fp8_attn_scale(ssp2_handle h, int layer);                     /* > 0, or 0 on a bad argument */
@@ -293,12 +294,41 @@ int ssp2_clone_weights(ssp2_handle dst, ssp2_handle src);
 int ssp2_prune_ffn_into(ssp2_handle dst, ssp2_handle src, int layer, const int32_t* keep_host, int n_keep);
 
 /* a2 standalone (the hook body on an activation tensor that already sits in HBM):
- *   act_dev bf16 (dtype 0) or f32 (dtype 1), [n, tokens, ld] with the first d columns used;
- *   out_dev f32 [ceil(n/group), out_stride] : out[g][j] = sum_{s in group g} sqrt(sum_t act[s,t,j]^2)
- *   (group <= 0: one group of n); norms_ws_dev f32 [2, n, ld] scratch (sums of squares of the two token halves).
- * HBM-bound: n*tokens*d*sizeof(act) bytes read once. */
+ *   act_dev bf16 (dtype 0) or f32 (dtype 1), [n, tokens, ld], ld >= d and a multiple of 8.  ALL ld columns are read and scored — the
+ *   pad columns [d, ld) too (the forward's activations hold zeros there) —, d only has to fit;
+ *   out_dev f32 [ceil(n/group), out_stride], out_stride >= ld (a smaller one is SSP2_EINVAL before anything is launched: columns
+ *   [0, ld) of every group's row are written) : out[g][j] = sum_{s in group g} sqrt(sum_t act[s,t,j]^2) for j < ld, columns
+ *   [ld, out_stride) untouched (group <= 0: one group of n); norms_ws_dev f32 [2, n, ld] scratch (sums of squares of the two token
+ *   halves).
+ * HBM-bound: n*tokens*ld*sizeof(act) bytes read once. */
 int ssp2_act_l2_accum(void* hip_stream, const void* act_dev, int dtype, int n, int tokens, int d, int ld,
                       int score_chain, int group, float* norms_ws_dev, float* out_dev, size_t out_stride);
+
+/* Additive (ABI stays 7): the FUSED score finish on its own — the two launches of the forward's stage-1 hook behind an fc1 epilogue that
+ * wrote the slab (ssp2_linear_bf16_ex / ssp2_linear_e4m3 with score_site; the forward calls the same function):
+ *   slab_dev f32 [2 * ceil(M / 256)][2][ld], M = ssp2_rows of (n, group) at `tokens` tokens per image: entry [t][seg] is the sum of
+ *   squares over the rows of 128-row tile t that belong to the image owning the tile's first row (seg 0) or to the following image
+ *   (seg 1); tokens >= 128, so a tile meets no third image.  n, tokens and group give the row layout (ssp2_rows) AND the scoring group
+ *   (group <= 0 or > n: one group of n);
+ *   norms_ws_dev f32 [n, ld] receives norm[s][j] = sqrt(sum of the slab entries that hold rows of image s), rounded to bf16 with
+ *   chain = SSP2_CHAIN_BF16_REF;
+ *   out_dev f32 [ceil(n / group), out_stride], out_stride >= ld >= 1: out[g][j] = sum over the images of group g, in index order, of
+ *   norm[s][j] (rounded to bf16 on the bf16 chain); columns [ld, out_stride) untouched.
+ * Every argument is checked before the device is touched. */
+int ssp2_score_finish(void* hip_stream, const float* slab_dev, int n, int tokens, int group, int ld, int score_chain,
+                      float* norms_ws_dev, float* out_dev, size_t out_stride);
+
+/* Additive (ABI stays 7): what the engine HOLDS for a tensor kind (SSP2_T_*) and layer, read back into host memory — for checks of the
+ * ingest, the width prune and the clone.  Synchronises the handle's stream and copies; no kernel runs, no state changes.
+ *   SSP2_PEEK_SHAPE  host int32 [5] = rows, cols, rows_pad, ld, ld8 (ld8 = 0 without an e4m3 image; a bias is rows = n, cols = 1,
+ *                    rows_pad, ld = 1; an fp32 vector rows = rows_pad = its length).  No device access at all.
+ *   SSP2_PEEK_IMAGE  a matrix: its bf16 image [rows_pad, ld]; a bias: f32 [rows_pad]; a vector (LayerNorm, cls, pos, dist): f32 [rows]
+ *   SSP2_PEEK_E4M3   a matrix in fp8 mode: its e4m3 image, bytes [rows_pad, ld8]
+ *   SSP2_PEEK_SCALE  ... and its dequantisation scales, f32 [rows_pad]
+ * `bytes` must be the size of what is asked for.  A wrong kind, layer, image or byte count is SSP2_EINVAL (an e4m3 image or scale of
+ * a bias or vector too); an e4m3 image that does not exist (bf16 engine; patch embedding and heads) is SSP2_ESTATE. */
+enum { SSP2_PEEK_SHAPE = 0, SSP2_PEEK_IMAGE = 1, SSP2_PEEK_E4M3 = 2, SSP2_PEEK_SCALE = 3 };
+int ssp2_peek_tensor(ssp2_handle h, int kind, int layer, int image, void* host, size_t bytes);
 
 /* a3's building block on its own — one nn.Linear of the forward with its fused epilogue, on caller-owned device buffers
  * (what `F.linear` under autocast computes at src/vit_pruning.py:180 inside the third-party model):
