@@ -108,6 +108,9 @@ struct ssp2_engine {
   // token layout (ssp2_create_ext): prefix tokens in front of the patches (1: CLS; 2: CLS + distillation token) and whether the
   // logits average the CLS head with a distillation head on row 1 (tail_rows = rows the evaluation tail carries: 2 with it, else 1)
   int prefix = 1, dist_head = 0, tail_rows = 1;
+  // (ssp2_create_layout) register tokens between CLS and the patches (prefix = 1 + reg_tokens; the head still reads row 0: tail_rows 1)
+  // and whether pos carries the prefix tokens' rows (1: tokens rows) or the patches' only (0: class-free positions, timm no_embed_class)
+  int reg_tokens = 0, pos_prefix_rows = 1;
   int kpe = 0, kpe_pad = 0, ld_int_max = 0;
   long rows_cap = 0;        // token-matrix rows the workspace is sized for
   hipStream_t stream = nullptr;
@@ -126,8 +129,10 @@ struct ssp2_engine {
 
   Mat patch, head, head_dist;
   float *cls = nullptr, *pos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr, *dist = nullptr;
+  float* reg = nullptr;     // register tokens, fp32 [reg_tokens, dim] as loaded (ssp2_set_reg_tokens)
   bool misc_set[4] = {false, false, false, false};
-  bool dist_set = false;
+  bool dist_set = false, reg_set = false;
+  size_t pos_rows() const { return (size_t)(pos_prefix_rows ? tokens : patches); }      // rows of SSP2_T_POS
   std::vector<Layer> layers;
 
   // workspace (sized for max_images)
@@ -632,11 +637,25 @@ int ssp2_create(const ssp2_vit_desc* desc, ssp2_handle* out) { return ssp2_creat
 int ssp2_create_opts(const ssp2_vit_desc* desc, const int32_t* opt, ssp2_handle* out) { return ssp2_create_ext(desc, opt, nullptr, out); }
 
 int ssp2_create_ext(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_vit_ext* ext, ssp2_handle* out) {
+  const ssp2_token_layout lay{ext ? ext->prefix_tokens : 1, ext ? ext->dist_head : 0, 0, 1};
+  return ssp2_create_layout(desc, opt, &lay, out);
+}
+
+int ssp2_create_layout(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_token_layout* layout, ssp2_handle* out) {
   if (!desc || !out || !desc->d_int) return fail(SSP2_EINVAL, "null argument");
-  const int prefix = ext ? ext->prefix_tokens : 1, dist_head = ext ? ext->dist_head : 0;
-  if (prefix < 1 || prefix > 2) return fail(SSP2_EINVAL, "prefix_tokens %d: 1 (CLS) or 2 (CLS + distillation token)", prefix);
+  const int prefix = layout ? layout->prefix_tokens : 1, dist_head = layout ? layout->dist_head : 0;
+  const int reg_tokens = layout ? layout->reg_tokens : 0, pos_prefix_rows = layout ? layout->pos_prefix_rows : 1;
+  if (reg_tokens < 0 || reg_tokens > 8) return fail(SSP2_EINVAL, "reg_tokens %d: 0 to 8 register tokens", reg_tokens);
+  if (pos_prefix_rows < 0 || pos_prefix_rows > 1)
+    return fail(SSP2_EINVAL, "pos_prefix_rows %d: 1 (positions for every token) or 0 (class-free positions: the patches' rows only)", pos_prefix_rows);
+  if (reg_tokens > 0 && prefix != 1 + reg_tokens)
+    return fail(SSP2_EINVAL, "prefix_tokens %d: CLS + reg_tokens = %d register tokens are %d prefix tokens", prefix, reg_tokens, 1 + reg_tokens);
+  if (prefix < 1 || (reg_tokens == 0 && prefix > 2)) return fail(SSP2_EINVAL, "prefix_tokens %d: 1 (CLS) or 2 (CLS + distillation token)", prefix);
   if (dist_head < 0 || dist_head > 1) return fail(SSP2_EINVAL, "dist_head %d: 0 (CLS head) or 1 (CLS and distillation heads averaged)", dist_head);
+  if (dist_head && reg_tokens > 0) return fail(SSP2_EINVAL, "dist_head = 1 with reg_tokens = %d: a distilled model has no register tokens", reg_tokens);
   if (dist_head && prefix != 2) return fail(SSP2_EINVAL, "dist_head = 1 reads the distillation token: it needs prefix_tokens = 2 (got %d)", prefix);
+  if (!pos_prefix_rows && (dist_head || (reg_tokens == 0 && prefix == 2)))
+    return fail(SSP2_EINVAL, "pos_prefix_rows = 0 with a distillation token (prefix_tokens %d, dist_head %d): a distilled model has positions for every token", prefix, dist_head);
   if (opt) {
     for (int i = 0; i < SSP2_OPT_COUNT; ++i)
       if (opt[i] < -1) return fail(SSP2_EINVAL, "option %d: override %d (-1 = environment default)", i, opt[i]);
@@ -647,17 +666,8 @@ int ssp2_create_ext(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_vi
   if (d.dim <= 0 || d.dim % 64 || d.dim > 2048) return fail(SSP2_EINVAL, "dim %d must be a multiple of 64, <= 2048", d.dim);
   if (d.heads <= 0 || d.dim % d.heads) return fail(SSP2_EINVAL, "dim %d not divisible by heads %d", d.dim, d.heads);
   if (d.depth <= 0 || d.classes <= 0 || d.max_images <= 0) return fail(SSP2_EINVAL, "depth/classes/max_images must be positive");
-  int dev_count = 0;
-  if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0)
-    return fail(SSP2_EHIP, "no HIP device visible: libssp2vit has no CPU path");
-
-  auto* e = new ssp2_engine();
+  auto* e = new ssp2_engine();      // (host state only until the geometry has been accepted: every SSP2_EINVAL below comes before the device is touched)
   e->d = d;
-  {
-    int dev = 0; hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) e->n_cu = pr.multiProcessorCount;
-    e->dev = (dev >= 0 && dev < kMaxDevices) ? dev : 0;
-  }
   {   // option defaults, each overridable ONCE by its environment variable (read here, never on a launch path)
     auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return (v && *v) ? atoi(v) : dflt; };
     e->opt[SSP2_OPT_ZIGZAG] = env_int("SSP2_ZIGZAG", 1);
@@ -705,6 +715,7 @@ int ssp2_create_ext(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_vi
   e->side = d.img / d.patch;
   e->patches = e->side * e->side;
   e->prefix = prefix; e->dist_head = dist_head; e->tail_rows = dist_head ? 2 : 1;
+  e->reg_tokens = reg_tokens; e->pos_prefix_rows = pos_prefix_rows;
   e->tokens = e->patches + prefix;
   e->dh = d.dim / d.heads;
   e->kpe = 3 * d.patch * d.patch;
@@ -723,6 +734,16 @@ int ssp2_create_ext(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_vi
     return fail(SSP2_EINVAL, "no attention kernel for head dim %d with %d tokens (head dim 64: up to 288 tokens, up to %d with SSP2_OPT_ATTN_STREAM; "
                              "80: 257..288; 16: up to 32)", dh, tk, ATTN_STREAM_MAX_TOKENS);
   }
+  int dev_count = 0;
+  if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0) {
+    delete e;
+    return fail(SSP2_EHIP, "no HIP device visible: libssp2vit has no CPU path");
+  }
+  {
+    int dev = 0; hipDeviceProp_t pr;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) e->n_cu = pr.multiProcessorCount;
+    e->dev = (dev >= 0 && dev < kMaxDevices) ? dev : 0;
+  }
   int rc = 0;
 #define TRY(x) do { if ((rc = (x))) { ssp2_destroy(e); return rc; } } while (0)
 #define TRYA(x) do { if (int rc_ = (x)) return rc_; } while (0)
@@ -731,8 +752,9 @@ int ssp2_create_ext(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_vi
   TRYA(mat_alloc(e, e->head, d.classes, d.dim));
   if (e->dist_head) TRYA(mat_alloc(e, e->head_dist, d.classes, d.dim));
   TRYA(dalloc(e, &e->cls, d.dim, false));
-  if (e->prefix == 2) TRYA(dalloc(e, &e->dist, d.dim, false));
-  TRYA(dalloc(e, &e->pos, (size_t)e->tokens * d.dim, false));
+  if (e->prefix == 2 && !e->reg_tokens) TRYA(dalloc(e, &e->dist, d.dim, false));
+  if (e->reg_tokens) TRYA(dalloc(e, &e->reg, (size_t)e->reg_tokens * d.dim, false));
+  TRYA(dalloc(e, &e->pos, e->pos_rows() * d.dim, false));
   TRYA(dalloc(e, &e->lnf_g, d.dim, false));
   TRYA(dalloc(e, &e->lnf_b, d.dim, false));
   e->layers.resize(d.depth);
@@ -762,7 +784,7 @@ int ssp2_create_ext(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_vi
   if (e->tokens < GEMM_BM) TRYA(dalloc(e, &e->prebuf, M * e->ld_int_max, true, false));
   TRYA(dalloc(e, &e->slab, tiles_m * 2 * e->ld_int_max, true));
   TRYA(dalloc(e, &e->norms, (size_t)2 * d.max_images * e->ld_int_max, true));   // [2 token halves][n][ld] for the standalone L2 kernel
-  const size_t pre_rows = (size_t)e->prefix * d.max_images;          // the tail's and the head's rows: prefix_tokens per image at most
+  const size_t pre_rows = (size_t)std::min(e->prefix, 2) * d.max_images;   // the tail's and the head's rows: tail_rows (<= 2) per image; register tokens add none
   TRYA(dalloc(e, &e->cls_h, pre_rows * d.dim, true));
   TRYA(dalloc(e, &e->x_cls, pre_rows * d.dim, true));
   TRYA(dalloc(e, &e->q_cls, pre_rows * d.dim, true));
@@ -1005,7 +1027,7 @@ static int resolve_tensor(ssp2_engine* e, int kind, int layer, IngestTarget* t) 
     case SSP2_T_PATCH_W: return mat(e->patch);
     case SSP2_T_PATCH_B: return bias(e->patch);
     case SSP2_T_CLS: return vec(e->cls, D, &e->misc_set[0]);
-    case SSP2_T_POS: return vec(e->pos, (size_t)e->tokens * D, &e->misc_set[1]);
+    case SSP2_T_POS: return vec(e->pos, e->pos_rows() * D, &e->misc_set[1]);      // (class-free positions: the patches' rows only)
     case SSP2_T_LN1_G: return vec(L->ln1_g, D, &L->ln_set[0]);
     case SSP2_T_LN1_B: return vec(L->ln1_b, D, &L->ln_set[1]);
     case SSP2_T_LN2_G: return vec(L->ln2_g, D, &L->ln_set[2]);
@@ -1095,6 +1117,21 @@ int ssp2_set_layer_scale(ssp2_handle e, int layer, int branch, const float* gamm
   return set_layer_scale_impl(e, e->layers[layer], branch, gamma, on_device != 0);
 }
 
+// Register tokens: fp32 in, fp32 held (parameters: the concat with the fp32 position sum keeps them as they are)
+static int set_reg_tokens_impl(ssp2_engine* e, const float* reg, bool dev) {
+  HIPCHK(hipMemcpyAsync(e->reg, reg, (size_t)e->reg_tokens * e->d.dim * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+  if (!dev) HIPCHK(hipStreamSynchronize(e->stream));
+  e->reg_set = true;
+  return 0;
+}
+int ssp2_set_reg_tokens(ssp2_handle e, const float* reg, int count, int on_device) {
+  if (!e) return fail(SSP2_EINVAL, "null handle");
+  if (count != e->reg_tokens || count <= 0)
+    return fail(SSP2_EINVAL, "set_reg_tokens: count %d, this engine has reg_tokens = %d (ssp2_create_layout)", count, e->reg_tokens);
+  if (!reg) return fail(SSP2_EINVAL, "set_reg_tokens: null reg");
+  return set_reg_tokens_impl(e, reg, on_device != 0);
+}
+
 static int check_n(ssp2_engine* e, int n, int group = 0) {
   if (!e) return fail(SSP2_EINVAL, "null handle");
   if (n <= 0 || n > e->d.max_images) return fail(SSP2_ESTATE, "n=%d outside (0, max_images=%d]", n, e->d.max_images);
@@ -1152,8 +1189,10 @@ int ssp2_embed(ssp2_handle e, const float* pixels_dev, int n, float* x_dev, int 
   const RowMap rm = make_rowmap(e->tokens, n, group);
   if (!pixels_dev || !x_dev) return fail(SSP2_EINVAL, "null device pointer");
   if (!(e->patch.w_set && e->patch.b_set && e->misc_set[0] && e->misc_set[1])) return fail(SSP2_ESTATE, "patch/cls/pos weights not loaded");
-  if (e->prefix == 2 && !e->dist_set) return fail(SSP2_ESTATE, "distillation token not loaded (SSP2_T_DIST)");
+  if (e->dist && !e->dist_set) return fail(SSP2_ESTATE, "distillation token not loaded (SSP2_T_DIST)");
+  if (e->reg_tokens && !e->reg_set) return fail(SSP2_ESTATE, "register tokens not loaded (ssp2_set_reg_tokens)");
   const int D = e->d.dim;
+  const int pos_row0 = e->pos_prefix_rows ? e->prefix : 0;      // position row of patch 0
   if (rm.group > 0) {   // pad rows between slabs must hold finite values: they flow through LN / GEMMs (never scored).  Only THEY are
     // zeroed (one strided fill: 4.7 MB for eight 64-image ViT-B/16 slabs; round 2 cleared all 310 MB of x per stage-1 launch)
     const int n_slabs = (n + rm.group - 1) / rm.group, pad_rows = rm.mpad - rm.group * rm.tokens;
@@ -1163,7 +1202,7 @@ int ssp2_embed(ssp2_handle e, const float* pixels_dev, int n, float* x_dev, int 
   {
     ProfScope ps(e, SSP2_K_OTHER);
     hipLaunchKernelGGL(cls_row_kernel, dim3((unsigned)(((long)n * e->prefix * D + 255) / 256)), dim3(256), 0, e->stream, x_dev, e->cls, e->pos, n, rm, D,
-                       e->dist, e->prefix);
+                       e->dist, e->prefix, e->reg, e->pos_prefix_rows);
     HIPCHK(hipGetLastError());
   }
   if (e->opt[SSP2_OPT_PATCH_LDS]) {
@@ -1172,7 +1211,7 @@ int ssp2_embed(ssp2_handle e, const float* pixels_dev, int n, float* x_dev, int 
     PatchArgs a{};
     a.px = pixels_dev; a.W = e->patch.w; a.ldw = e->patch.ld; a.bias = e->patch.b; a.pos = e->pos; a.x = x_dev; a.ldx = D;
     a.n = n; a.img = e->d.img; a.p = e->d.patch; a.side = e->side; a.K = e->kpe; a.Kpad = e->kpe_pad; a.N = D;
-    a.tiles_n = e->patch.rows_pad / GEMM_BN; a.rm = rm; a.prefix = e->prefix;
+    a.tiles_n = e->patch.rows_pad / GEMM_BN; a.rm = rm; a.prefix = e->prefix; a.pos_row0 = pos_row0;
     const int tiles_m = (n * e->patches + GEMM_BM - 1) / GEMM_BM;
     static bool attr_done[kMaxDevices] = {};
     if (!attr_done[e->dev]) {
@@ -1199,7 +1238,7 @@ int ssp2_embed(ssp2_handle e, const float* pixels_dev, int n, float* x_dev, int 
     HIPCHK(hipGetLastError());
   }
   GemmArgs g = bind(e->patch, act_bf16(e->a_pe, e->kpe_pad), n * e->patches, D);
-  g.x = x_dev; g.ldx = D; g.pos = e->pos; g.patches = e->patches; g.prefix = e->prefix; g.group = rm.group; g.mpad = rm.mpad; g.n_img = n;
+  g.x = x_dev; g.ldx = D; g.pos = e->pos; g.patches = e->patches; g.prefix = e->prefix; g.pos_row0 = pos_row0; g.group = rm.group; g.mpad = rm.mpad; g.n_img = n;
   return launch_gemm<EPI_PATCH>(e, g, SSP2_K_GEMM_PATCH);
 }
 
@@ -1621,13 +1660,17 @@ int ssp2_clone_weights(ssp2_handle dst, ssp2_handle src) {
     return fail(SSP2_EINVAL, "clone: the two engines describe different architectures");
   if (dst->prefix != src->prefix || dst->dist_head != src->dist_head)
     return fail(SSP2_EINVAL, "clone: token layouts differ (prefix_tokens %d / %d, dist_head %d / %d)", dst->prefix, src->prefix, dst->dist_head, src->dist_head);
+  if (dst->reg_tokens != src->reg_tokens || dst->pos_prefix_rows != src->pos_prefix_rows)
+    return fail(SSP2_EINVAL, "clone: token layouts differ (reg_tokens %d / %d, pos_prefix_rows %d / %d)", dst->reg_tokens, src->reg_tokens,
+                dst->pos_prefix_rows, src->pos_prefix_rows);
   const int D = a.dim;
   int rc;
   auto cp = [&](float* d, const float* s, size_t n) -> int { HIPCHK(hipMemcpyAsync(d, s, n * 4, hipMemcpyDeviceToDevice, dst->stream)); return 0; };
   if ((rc = copy_mat(dst, dst->patch, src->patch)) || (rc = copy_mat(dst, dst->head, src->head))) return rc;
-  if ((rc = cp(dst->cls, src->cls, D)) || (rc = cp(dst->pos, src->pos, (size_t)dst->tokens * D)) || (rc = cp(dst->lnf_g, src->lnf_g, D)) || (rc = cp(dst->lnf_b, src->lnf_b, D))) return rc;
+  if ((rc = cp(dst->cls, src->cls, D)) || (rc = cp(dst->pos, src->pos, dst->pos_rows() * D)) || (rc = cp(dst->lnf_g, src->lnf_g, D)) || (rc = cp(dst->lnf_b, src->lnf_b, D))) return rc;
   for (int i = 0; i < 4; ++i) dst->misc_set[i] = src->misc_set[i];
   if (src->dist) { if ((rc = cp(dst->dist, src->dist, D))) return rc; dst->dist_set = src->dist_set; }
+  if (src->reg) { if ((rc = cp(dst->reg, src->reg, (size_t)src->reg_tokens * D))) return rc; dst->reg_set = src->reg_set; }
   if (src->dist_head && (rc = copy_mat(dst, dst->head_dist, src->head_dist))) return rc;
   for (int l = 0; l < a.depth; ++l) {
     Layer &d = dst->layers[l]; const Layer& s = src->layers[l];

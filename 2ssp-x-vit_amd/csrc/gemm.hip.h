@@ -20,7 +20,8 @@
 //   EPI_RESID  x  += float(bf16(acc + bias))                            attention out-proj, fc2 (+residual)
 //   EPI_FC1    pre = bf16(acc + bias); out = bf16(gelu(pre));           fc1 + GELU + fused stage-1 score:
 //              per-(sample, neuron) partial sum of squares over this tile's tokens -> slab (2 segments/tile)
-//   EPI_PATCH  x[img*N + P + p] = float(bf16(acc + bias)) + pos[P + p]  patch-embed conv as GEMM (P = prefix tokens: CLS [+ DIST])
+//   EPI_PATCH  x[img*N + P + p] = float(bf16(acc + bias)) + pos[R + p]  patch-embed conv as GEMM (P = prefix tokens: CLS [+ DIST | + registers];
+//              R = pos_row0: P with positions for every token, 0 with class-free positions)
 //   EPI_F32    out_f32 = float(bf16(acc + bias))                        classifier head (tiny, scalar stores)
 //   EPI_RESID_LS  x = xin + fl32(ls[n] * float(bf16(acc + bias)))         EPI_RESID with LayerScale: the branch's per-column fp32 scale,
 //              product and sum rounded separately (common.hip.h ls_scale_add)
@@ -53,7 +54,8 @@ struct GemmArgs {
   int group, mpad, n_img;     // slab layout of the rows (RowMap); group == 0: contiguous
   float* slab; int slab_ld;   // [tiles_m][2][slab_ld]
   // EPI_PATCH
-  const float* pos; int patches; int prefix;   // prefix: tokens in front of the patches (1: CLS; 2: CLS + DIST)
+  const float* pos; int patches; int prefix;   // prefix: tokens in front of the patches (1: CLS; 2: CLS + DIST; 1 + R: CLS + registers)
+  int pos_row0;               // EPI_PATCH: position row of patch 0 (prefix, or 0 for class-free positions)
   int group_m;                // row tiles per L2 super-tile (0 = plain N-fastest order)
   int nt_out;                 // gemm256 kernel: bf16 / e4m3 activation outputs leave as NON-TEMPORAL stores (SSP2_OPT_NT_STORES)
   int reverse;                // gemm256: walk the tiles from the last to the first (see engine.hip, zigzag)
@@ -441,7 +443,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs g) {
         const int img = mc / g.patches, p = mc - img * g.patches;
         const RowMap rm{g.patches + g.prefix, g.group, g.mpad};
         dst[it] = g.x + (size_t)(row_of(rm, img) + g.prefix + p) * g.ldx + col0 + c;
-        xin[it] = *(const f32x4*)(g.pos + (size_t)(g.prefix + p) * g.ldx + col0 + c);
+        xin[it] = *(const f32x4*)(g.pos + (size_t)(g.pos_row0 + p) * g.ldx + col0 + c);
       }
     }
 #pragma unroll

@@ -33,7 +33,7 @@ __global__ void im2col_patch_kernel(const float* __restrict__ px, bf16* __restri
   }
 }
 
-// x[img*N + 0] = cls + pos[0]   (fp32; the concat promotes to fp32 under autocast)
+// x[img*N + t] = prefix token t (+ pos[t])   (fp32; the concat promotes to fp32 under autocast): cls_row_kernel below
 // What the hardware calls the XCD a workgroup runs on (HW_REG_XCC_ID, bits 3:0) — the fused LayerNorm of gemm256.hip.h keys its
 // work queues on it; the engine looks at one grid's worth of answers at create time.
 __global__ void xcc_probe_kernel(unsigned int* __restrict__ ids) {
@@ -43,13 +43,18 @@ __global__ void xcc_probe_kernel(unsigned int* __restrict__ ids) {
 }
 
 __global__ void cls_row_kernel(float* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos,
-                               int n, RowMap rm, int dim, const float* __restrict__ dist = nullptr, int prefix = 1) {
-  // prefix rows of every image: row 0 = cls + pos[0], row 1 (distilled models) = dist + pos[1]
+                               int n, RowMap rm, int dim, const float* __restrict__ dist = nullptr, int prefix = 1,
+                               const float* __restrict__ reg = nullptr, int pos_rows = 1) {
+  // prefix rows of every image (prefix <= 9): row 0 from cls; row t >= 1 from the register tokens reg[t - 1] ([prefix - 1, dim]) or,
+  // reg == nullptr (distilled models, prefix 2), from dist.  pos_rows = 1: + pos[t] (positions for every token); pos_rows = 0
+  // (class-free positions: pos holds the patches' rows only) the fp32 parameter itself, no add
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < (long)n * prefix * dim) {
     const int r = (int)(i / dim), d = (int)(i - (long)r * dim);
     const int im = r / prefix, t = r - im * prefix;
-    x[(size_t)(row_of(rm, im) + t) * dim + d] = (t ? dist : cls)[d] + pos[(size_t)t * dim + d];
+    const float* src = t == 0 ? cls : (reg ? reg + (size_t)(t - 1) * dim : dist);
+    const float v = src[d];
+    x[(size_t)(row_of(rm, im) + t) * dim + d] = pos_rows ? v + pos[(size_t)t * dim + d] : v;
   }
 }
 

@@ -1,6 +1,7 @@
 // Patch embedding (conv k = s = p as a GEMM) with the patch tiles staged through LDS straight from the fp32 pixels:
 //
-//   x[row(img) + P + q, :] = float(bf16(sum_k bf16(pixel[img, q, k]) * W[:, k] + bias)) + pos[P + q, :]   (P = prefix tokens: 1, or 2 with a distillation token)
+//   x[row(img) + P + q, :] = float(bf16(sum_k bf16(pixel[img, q, k]) * W[:, k] + bias)) + pos[R + q, :]
+//   (P = prefix tokens: CLS [+ DIST], or CLS + up to 8 register tokens; R = P with positions for every token, 0 with class-free positions)
 //
 // Round 1-2 went pixels -> im2col_patch_kernel -> bf16 matrix in HBM (154 MB per 512 images, written and read back) ->
 // gemm_bf16_kernel<EPI_PATCH>.  Here the A operand never exists in HBM: a workgroup gathers its 128 patches x 64 k-elements
@@ -17,12 +18,13 @@ struct PatchArgs {
   const float* px;            // [n, 3, img, img] fp32 NCHW
   const bf16* W; int ldw;     // [dim_pad, Kpad] bf16, k = c*p*p + ky*p + kx, zero beyond K
   const float* bias;          // [dim_pad]
-  const float* pos;           // [tokens, dim] fp32
+  const float* pos;           // [pos_row0 + patches, dim] fp32
   float* x; int ldx;          // residual stream, row layout rm
   int n, img, p, side, K, Kpad, N;
   int tiles_n;
   RowMap rm;                  // tokens = patches + prefix
-  int prefix;                 // tokens in front of the patches (1: CLS; 2: CLS + distillation token)
+  int prefix;                 // tokens in front of the patches (1: CLS; 2: CLS + distillation token; 1 + R: CLS + R register tokens)
+  int pos_row0;               // position row of patch 0: prefix (positions for every token) or 0 (class-free positions)
 };
 
 #define PATCH_LDS_BYTES (4 * GEMM_STAGE_BYTES)     // A0 A1 B0 B1; the fp32 epilogue staging (4 x 16 KiB) reuses all of it
@@ -200,7 +202,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (m < M) {
       const int im = m / patches, q = m - im * patches;
       const f32x4 v = *(const f32x4*)(stg + r * 256 + c * 4);
-      const f32x4 ps = *(const f32x4*)(g.pos + (size_t)(g.prefix + q) * g.ldx + col0 + c);
+      const f32x4 ps = *(const f32x4*)(g.pos + (size_t)(g.pos_row0 + q) * g.ldx + col0 + c);
       *(f32x4*)(g.x + (size_t)(row_of(g.rm, im) + g.prefix + q) * g.ldx + col0 + c) = ps + v;
     }
   }

@@ -161,7 +161,7 @@ int main(int argc, char** argv) {
   GemmArgs g{};
   g.A = A; g.lda = K; g.W = W; g.ldw = K; g.bias = bias; g.M = M; g.N = N; g.K = K;
   g.tiles_m = (M + 127) / 128; g.tiles_n = Npad / 128; g.out = out; g.ldo = Npad; g.x = x; g.ldx = Npad; g.ls = ls;
-  g.score_site = (epi == 2 || epi == 13) ? 1 : ((epi == 5 || epi == 14) ? 2 : 0); g.tokens = tokens; g.slab = slab; g.slab_ld = Npad; g.pos = pos; g.patches = 196; g.prefix = 1; g.group_m = argc > 7 ? atoi(argv[7]) : 0;
+  g.score_site = (epi == 2 || epi == 13) ? 1 : ((epi == 5 || epi == 14) ? 2 : 0); g.tokens = tokens; g.slab = slab; g.slab_ld = Npad; g.pos = pos; g.patches = 196; g.prefix = 1; g.pos_row0 = 1; g.group_m = argc > 7 ? atoi(argv[7]) : 0;
 #ifdef GEMM_STAMPS
   unsigned long long* stamps; CK(hipMalloc(&stamps, (size_t)g.tiles_m * g.tiles_n * 64 * 8)); CK(hipMemset(stamps, 0, (size_t)g.tiles_m * g.tiles_n * 64 * 8));
   g.stamps = stamps;

@@ -27,6 +27,7 @@ SYMBOLS = [
     "ssp2_create_opts", "ssp2_attention_stream_bf16", "ssp2_create_ext", "ssp2_attention_prefix_bf16",
     "ssp2_set_layer_scale", "ssp2_linear_ls_bf16", "ssp2_linear_ls_e4m3", "ssp2_linear_bf16_ex",
     "ssp2_attention_stream_e4m3", "ssp2_score_finish", "ssp2_peek_tensor",
+    "ssp2_create_layout", "ssp2_set_reg_tokens",
 ]
 
 T_KINDS = ["patch_w", "patch_b", "cls", "pos", "ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b",
@@ -54,6 +55,11 @@ class VitDesc(C.Structure):
 class VitExt(C.Structure):
     """ssp2_vit_ext: the token layout of ssp2_create_ext (prefix tokens 1 / 2, distillation head 0 / 1)."""
     _fields_ = [("prefix_tokens", C.c_int32), ("dist_head", C.c_int32)]
+
+
+class TokenLayout(C.Structure):
+    """ssp2_token_layout: ssp2_create_layout's token layout (VitExt's two fields, register tokens 0..8, pos rows for the prefix 1 / 0)."""
+    _fields_ = [("prefix_tokens", C.c_int32), ("dist_head", C.c_int32), ("reg_tokens", C.c_int32), ("pos_prefix_rows", C.c_int32)]
 
 
 class Ssp2Error(RuntimeError):
@@ -229,6 +235,8 @@ def load(build_if_missing: bool = True, variant: Optional[str] = None) -> C.CDLL
     lib.ssp2_create.argtypes = [C.POINTER(VitDesc), C.POINTER(vp)]
     lib.ssp2_create_opts.argtypes = [C.POINTER(VitDesc), C.POINTER(i32), C.POINTER(vp)]
     lib.ssp2_create_ext.argtypes = [C.POINTER(VitDesc), C.POINTER(i32), C.POINTER(VitExt), C.POINTER(vp)]
+    lib.ssp2_create_layout.argtypes = [C.POINTER(VitDesc), C.POINTER(i32), C.POINTER(TokenLayout), C.POINTER(vp)]
+    lib.ssp2_set_reg_tokens.argtypes = [vp, vp, i32, i32]
     lib.ssp2_destroy.argtypes = [vp]
     lib.ssp2_set_stream.argtypes = [vp, vp]
     lib.ssp2_load_tensor.argtypes = [vp, i32, i32, C.POINTER(C.c_float), C.c_size_t]

@@ -8,8 +8,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
-from ._lib import EXT_OPTIONS, K_CLASS, OPTIONS, SCORE_CHAIN, SCORE_SITE, T_KINDS, Ssp2Error, VitDesc, VitExt, check
+from . import _lib, weights as _weights
+from ._lib import EXT_OPTIONS, K_CLASS, OPTIONS, SCORE_CHAIN, SCORE_SITE, T_KINDS, Ssp2Error, TokenLayout, VitDesc, VitExt, check
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -42,6 +42,9 @@ class VitEngine:
         persistent kernels do (set_option("fp8_proj", 0) keeps both on bf16).  A twin inherits it.
         Token layout: `weights["prefix_tokens"]` (default 1; 2 = CLS + distillation token, DeiT) and a distillation head when the
         dictionary has `head_dist_w` (logits = mean of the CLS and DIST heads) go to ssp2_create_ext; a twin inherits them too.
+        Register tokens (`weights["reg"]`, [1, R, dim] with prefix_tokens = 1 + R, R <= 8) and class-free positions
+        (`weights["no_embed_class"]`: `pos` has the patches' rows only, the prefix tokens get no position row) go to ssp2_create_layout
+        and ssp2_set_reg_tokens; the head reads CLS; a twin and a derived engine inherit the layout.
         LayerScale: `weights["ls1.i"]` / `weights["ls2.i"]` (fp32 [dim]: timm Block.ls1 / ls2 gamma) scale block i's attention / MLP
         branch before the residual add (ssp2_set_layer_scale); a block without the key runs the plain residual epilogue.  The lab
         build's options ln_fusion / defer_resid are not extended to such a branch: it takes the product kernel form."""
@@ -58,6 +61,7 @@ class VitEngine:
             stream_fp8 = bool(src.stream_fp8)
             weights = dict(depth=src.depth, dim=src.dim, classes=src.classes, img=src.img, patch=src.patch, heads=src.heads,
                            eps=src.eps, prefix_tokens=src.prefix_tokens, dist_head=src.dist_head, _layer_scale=src.layer_scale,
+                           _reg_tokens=src.reg_tokens, no_embed_class=src.no_embed_class,
                            **{f"fc1_w.{i}": torch.empty(int(d), 0) for i, d in enumerate(_d_int)})
             device = src.device
         if not torch.cuda.is_available():
@@ -76,6 +80,11 @@ class VitEngine:
         self.patch, self.heads, self.eps = int(weights["patch"]), int(weights["heads"]), float(weights.get("eps", 1e-6))
         self.prefix_tokens = int(weights.get("prefix_tokens", 1))
         self.dist_head = int(weights.get("dist_head", "head_dist_w" in weights))
+        self.reg_tokens, self.no_embed_class = self._position_layout_of(weights)
+        if self.reg_tokens and self.prefix_tokens != 1 + self.reg_tokens:
+            raise ValueError(f"prefix_tokens={self.prefix_tokens}: CLS + {self.reg_tokens} register token(s) (reg) are {1 + self.reg_tokens}")
+        if _twin_of is None and (self.reg_tokens or self.no_embed_class):
+            _weights.check_flat_layout(weights)                  # pos rows against img / patch, no distillation token beside registers
         self.d_int = [int(weights[f"fc1_w.{i}"].shape[0]) for i in range(self.depth)]
         self.layer_scale = self._layer_scale_of(weights, self.depth, self.dim)      # per block: (ls1 present, ls2 present)
         self.score_ld = max((d + 63) // 64 * 64 for d in self.d_int)
@@ -89,7 +98,10 @@ class VitEngine:
             opts = (C.c_int32 * _lib.OPT_COUNT)(*([-1] * _lib.OPT_COUNT))
             if attn_stream is not None:
                 opts[OPTIONS["attn_stream"]] = int(attn_stream)
-            if self.prefix_tokens == 1 and not self.dist_head:
+            if self.reg_tokens or self.no_embed_class:
+                lay = TokenLayout(self.prefix_tokens, self.dist_head, self.reg_tokens, 0 if self.no_embed_class else 1)
+                self._check(self.lib.ssp2_create_layout(C.byref(desc), opts, C.byref(lay), C.byref(h)))
+            elif self.prefix_tokens == 1 and not self.dist_head:
                 self._check(self.lib.ssp2_create_opts(C.byref(desc), opts, C.byref(h)))
             else:
                 ext = VitExt(self.prefix_tokens, self.dist_head)
@@ -122,6 +134,16 @@ class VitEngine:
                     raise ValueError(f"{k}: a LayerScale gamma of {int(w[k].numel())} values on a hidden size of {dim}")
         return tuple((f"ls1.{i}" in w, f"ls2.{i}" in w) for i in range(depth))
 
+    @staticmethod
+    def _position_layout_of(w: Dict) -> Tuple[int, bool]:
+        """(register tokens, class-free positions) of `w`: rows of `reg` ([1, R, dim]) and `no_embed_class`."""
+        if "_reg_tokens" in w:
+            return int(w["_reg_tokens"]), bool(w.get("no_embed_class", False))
+        reg = w.get("reg")
+        if reg is not None and (reg.dim() != 3 or int(reg.shape[0]) != 1 or int(reg.shape[2]) != int(w["dim"])):
+            raise ValueError(f"reg: shape {tuple(reg.shape)} is not [1, R, {int(w['dim'])}]")
+        return (int(reg.shape[1]) if reg is not None else 0), bool(w.get("no_embed_class", False))
+
     def _load(self, w: Dict) -> None:
         """fp32 tensors in nn.Linear layout -> the engine's bf16 / padded weight image.  The rounding and the padding run
         in a kernel; a tensor that already lives on this GPU (a module moved to the device, as the reference keeps it)
@@ -141,7 +163,7 @@ class VitEngine:
                                                 C.cast(t.data_ptr(), C.POINTER(C.c_float)), t.numel()))
         for k in ("patch_w", "patch_b", "cls", "pos", "lnf_g", "lnf_b", "head_w", "head_b"):
             put(k, 0, w[k])
-        if self.prefix_tokens == 2:
+        if self.prefix_tokens == 2 and not self.reg_tokens:
             put("dist", 0, w["dist"])
         if self.dist_head:
             put("head_dist_w", 0, w["head_dist_w"]); put("head_dist_b", 0, w["head_dist_b"])
@@ -158,6 +180,12 @@ class VitEngine:
             ptrs = (C.c_void_p * m)(*[b[2].data_ptr() for b in batch])
             numels = (C.c_size_t * m)(*[b[2].numel() for b in batch])
             self._check(self.lib.ssp2_load_tensors_dev(self.h, m, kinds, layers, ptrs, numels))
+        if self.reg_tokens:                                      # register tokens: fp32 as they are, one small copy (no tensor kind: the kinds' order is pinned)
+            t = w["reg"].detach()
+            on_dev = t.device == self.device
+            t = (t if on_dev else t.to("cpu")).to(torch.float32).contiguous().view(-1)
+            keep.append(t)
+            self._check(self.lib.ssp2_set_reg_tokens(self.h, _ptr(t), self.reg_tokens, int(on_dev)))
         # LayerScale: fp32 as it is, one small copy per branch (no tensor kind of the batched ingest: the kinds' order is pinned)
         for i, has in enumerate(self.layer_scale):
             for br in (0, 1):
@@ -173,7 +201,8 @@ class VitEngine:
     def geometry_key(self):
         """What two engines must share for one to take over the other's handle (workspace, weight storage): see `reload`."""
         return (str(self.device), self.precision, self.lib_variant, self.img, self.patch, self.dim, self.heads, self.depth, self.classes,
-                float(self.eps), tuple(int(d) for d in self.d_int), self.prefix_tokens, self.dist_head, self.layer_scale)
+                float(self.eps), tuple(int(d) for d in self.d_int), self.prefix_tokens, self.dist_head, self.layer_scale,
+                self.reg_tokens, self.no_embed_class)
 
     def reload(self, weights: Dict) -> "VitEngine":
         """Another model of the SAME geometry into this engine: every tensor is ingested again (device-to-device rounding kernels), the
@@ -186,6 +215,10 @@ class VitEngine:
             raise Ssp2Error("reload: FFN widths differ")
         if (int(weights.get("prefix_tokens", 1)), int(weights.get("dist_head", "head_dist_w" in weights))) != (self.prefix_tokens, self.dist_head):
             raise Ssp2Error("reload: token layouts differ (prefix tokens / distillation head)")
+        if self._position_layout_of(weights) != (self.reg_tokens, self.no_embed_class):
+            raise Ssp2Error("reload: token layouts differ (register tokens / class-free positions)")
+        if self.reg_tokens or self.no_embed_class:
+            _weights.check_flat_layout(weights)
         if self._layer_scale_of(weights, self.depth, self.dim) != self.layer_scale:
             raise Ssp2Error("reload: LayerScale differs (which residual branches carry a gamma)")
         with torch.cuda.device(self.device):

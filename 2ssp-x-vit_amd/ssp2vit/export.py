@@ -34,7 +34,13 @@ def pruning_meta(model) -> Dict[str, Any]:
     heads = getattr(cfg, "num_attention_heads", None)
     # `layout` = the key layout of the saved state dict; `origin_layout` / `score_site` / `layer_norm_eps` = model facts a key layout
     # does not carry (an HF-origin model held in the timm-layout container still hooks post-GELU and normalises with eps 1e-12)
-    return {"layout": kind, "origin_layout": getattr(model, "ssp2_origin_layout", kind), "score_site": site,
+    extra = {}
+    if kind == "timm" and (getattr(model, "no_embed_class", False) or getattr(model, "reg_token", None) is not None):
+        # a state dict cannot say no_embed_class, and at toy sizes pos_embed's row count alone does not either: both travel in the meta
+        patch = int(model.patch_embed.proj.weight.shape[-1])
+        rows = int(model.pos_embed.shape[1]) - (0 if getattr(model, "no_embed_class", False) else int(getattr(model, "num_prefix_tokens", 1)))
+        extra = {"no_embed_class": bool(getattr(model, "no_embed_class", False)), "img_size": int(round(rows ** 0.5)) * patch}
+    return {**extra, "layout": kind, "origin_layout": getattr(model, "ssp2_origin_layout", kind), "score_site": site,
             "layer_norm_eps": None if eps is None else float(eps), "num_attention_heads": None if heads is None else int(heads),
             "num_blocks": len(blocks), "ffn_width_per_block": widths, "attention_removed_blocks": absent,
             "total_params": _vp.count_total_params(model)}
@@ -47,7 +53,7 @@ def _config_dict(model) -> Dict[str, Any]:
     hidden, inters = _vp._get_hidden_and_inter_sizes(model)
     out = {"model_type": "vit", "hidden_size": int(hidden), "num_hidden_layers": len(inters),
            "intermediate_size": int(max(inters)) if inters else None}
-    for k in ("num_attention_heads", "num_labels", "image_size", "patch_size", "layer_norm_eps"):
+    for k in ("num_attention_heads", "num_labels", "image_size", "patch_size", "layer_norm_eps", "no_embed_class"):
         v = getattr(cfg, k, None) if cfg is not None else None
         if v is not None:
             out[k] = v

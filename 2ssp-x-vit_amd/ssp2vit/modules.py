@@ -62,7 +62,8 @@ class _PatchEmbed(nn.Module):
 class EngineViT(nn.Module):
     """timm-layout container (`.blocks[i].{norm1,attn.qkv,attn.proj,norm2,mlp.fc1,mlp.fc2}`, `.patch_embed.proj`,
     `.cls_token`, `.pos_embed`, `.norm`, `.head`; distilled DeiT weights add timm's `.dist_token` and `.head_dist`, LayerScale weights
-    `.blocks[i].ls1.gamma` / `.ls2.gamma`); `model(px)`
+    `.blocks[i].ls1.gamma` / `.ls2.gamma`, register tokens timm's `.reg_token` [1, R, dim]; `.no_embed_class`, `.num_prefix_tokens`,
+    `.num_reg_tokens` and `.global_pool = "token"` say the token layout as timm's VisionTransformer does); `model(px)`
     returns logits computed by libssp2vit."""
 
     def __init__(self, w: Dict):
@@ -72,7 +73,12 @@ class EngineViT(nn.Module):
         self.patch_embed = _PatchEmbed(dim, int(w["patch"]))
         self.cls_token = nn.Parameter(torch.zeros(1, 1, dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, w["pos"].shape[1], dim))
-        if int(w.get("prefix_tokens", 1)) == 2:
+        regs = int(w["reg"].shape[1]) if w.get("reg") is not None else 0
+        if regs:
+            self.reg_token = nn.Parameter(torch.zeros(1, regs, dim))
+        self.no_embed_class = bool(w.get("no_embed_class", False))
+        self.num_prefix_tokens, self.num_reg_tokens, self.global_pool = int(w.get("prefix_tokens", 1)), regs, "token"
+        if int(w.get("prefix_tokens", 1)) == 2 and not regs:
             self.dist_token = nn.Parameter(torch.zeros(1, 1, dim))
         self.blocks = nn.ModuleList([_EngineBlock(dim, heads, int(w[f"fc1_w.{i}"].shape[0]), eps, f"ls1.{i}" in w, f"ls2.{i}" in w)
                                      for i in range(depth)])
@@ -82,6 +88,8 @@ class EngineViT(nn.Module):
             self.head_dist = nn.Linear(dim, int(w["classes"]))
         self.config = SimpleNamespace(hidden_size=dim, num_attention_heads=heads, num_labels=int(w["classes"]),
                                       image_size=int(w["img"]), patch_size=int(w["patch"]), layer_norm_eps=eps)
+        if self.no_embed_class:
+            self.config.no_embed_class = True
         self.ssp2_origin_layout = str(w.get("origin_layout") or w.get("layout") or "timm")     # where the weights came from (export writes it)
         with torch.no_grad():
             put = lambda p, t: p.copy_(t.reshape(p.shape))
@@ -99,6 +107,8 @@ class EngineViT(nn.Module):
                         put(getattr(b, name).gamma, w[f"{name}.{i}"])
             put(self.norm.weight, w["lnf_g"]); put(self.norm.bias, w["lnf_b"])
             put(self.head.weight, w["head_w"]); put(self.head.bias, w["head_b"])
+            if regs:
+                put(self.reg_token, w["reg"])
             if hasattr(self, "dist_token"):
                 put(self.dist_token, w["dist"])
             if hasattr(self, "head_dist"):

@@ -102,13 +102,16 @@ def plan_from_stats(st: ModelStats, target_sparsity: float, min_remaining: int =
 
 
 def stats_from_shapes(dim: int, depth: int, inter: Sequence[int] | int, classes: int, tokens: int, patch: int,
-                      layer_scale: int = 0) -> ModelStats:
+                      layer_scale: int = 0, reg_tokens: int = 0, no_embed_class: bool = False) -> ModelStats:
     """Parameter counts of a standard ViT (fused or split qkv count the same).  `layer_scale`: LayerScale vectors per block (2 for
     timm's ls1 + ls2): they count in the total, as in the reference's model.parameters(), and in neither the attention nor the FFN
-    count (the reference reads those from the attn / mlp sub-modules)."""
+    count (the reference reads those from the attn / mlp sub-modules).  `tokens` counts every token (patches + CLS + registers);
+    `reg_tokens` register tokens add `reg_tokens * dim` (timm's reg_token) and `no_embed_class` takes the `1 + reg_tokens` prefix rows
+    out of pos_embed — both in the total only, as model.parameters() has them."""
     inters = list(inter) if not isinstance(inter, int) else [inter] * depth
     attn = [4 * dim * dim + 4 * dim] * depth
     ffn = [d * dim + d + dim * d + dim for d in inters]
     blocks = sum(a + f + 4 * dim + layer_scale * dim for a, f in zip(attn, ffn))
-    total = blocks + (3 * patch * patch * dim + dim) + dim + tokens * dim + 2 * dim + (classes * dim + classes)
+    pos_rows = tokens - (1 + reg_tokens if no_embed_class else 0)
+    total = blocks + (3 * patch * patch * dim + dim) + dim + reg_tokens * dim + pos_rows * dim + 2 * dim + (classes * dim + classes)
     return ModelStats(total, dim, inters, attn, ffn)

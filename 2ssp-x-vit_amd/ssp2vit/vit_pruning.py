@@ -163,7 +163,7 @@ def engine_for(model, device="cuda", max_images: int = 64, precision: Optional[s
     attn_stream = attn_stream_setting(attn_stream)
     stream_fp8 = stream_fp8_setting(stream_fp8)
     key = id(model)
-    fp = _fingerprint(model) + (precision, attn_stream, stream_fp8) + _weights.token_layout(model) + (_weights.has_layer_scale(model),)
+    fp = _fingerprint(model) + (precision, attn_stream, stream_fp8) + _weights.token_layout(model) + (_weights.has_layer_scale(model),) + _weights.position_layout(model)
     hit = _ENGINES.get(key)
     if hit is not None and hit[0] == fp and hit[1].max_images >= max_images:
         return hit[1]
@@ -216,6 +216,7 @@ def _from_pool(flat, dev, max_images: int, precision: str, attn_stream: int = 0)
             same = (str(e.device) == str(dev) and e.precision == precision and e.max_images >= max_images and e.lib_variant is None
                     and getattr(e, "attn_stream", 0) == attn_stream
                     and (e.prefix_tokens, e.dist_head) == (int(flat.get("prefix_tokens", 1)), int("head_dist_w" in flat))
+                    and (e.reg_tokens, e.no_embed_class) == (_weights.reg_tokens_of(flat), bool(flat.get("no_embed_class", False)))
                     and tuple(e.layer_scale) == tuple((f"ls1.{l}" in flat, f"ls2.{l}" in flat) for l in range(e.depth))
                     and (e.img, e.patch, e.dim, e.heads, e.depth, e.classes) == tuple(int(flat[k]) for k in ("img", "patch", "dim", "heads", "depth", "classes"))
                     and abs(e.eps - float(flat.get("eps", 1e-6))) < 1e-15
@@ -247,7 +248,10 @@ def _tokens_of(model) -> int:
         try:
             for name in path.split("."):
                 obj = getattr(obj, name)
-            return int(obj.shape[1])
+            rows = int(obj.shape[1])
+            if path == "pos_embed" and getattr(model, "no_embed_class", False):      # class-free positions: the prefix tokens have no row
+                rows += int(getattr(model, "num_prefix_tokens", 1) or 1)
+            return rows
         except AttributeError:
             continue
     return 197

@@ -15,11 +15,15 @@ Keys (all tensors fp32, CPU, contiguous; layer index ``i`` in ``0..depth-1``)::
     prefix_tokens                                    1 (CLS), or 2 (CLS + distillation token: distilled DeiT); default 1
     dist [1,1,dim]                                   the distillation token (prefix_tokens == 2)
     head_dist_w [classes,dim]  head_dist_b [classes] the distillation head: logits = (head(CLS) + head_dist(DIST)) / 2
+    reg [1,R,dim]                                    register tokens between CLS and the patches (timm reg_token, R = 1..8):
+                                                     prefix_tokens = 1 + R; kept fp32, never rounded; not together with dist
+    no_embed_class                                   bool, default False.  True (timm no_embed_class: DeiT-III, DINOv2-reg): pos is
+                                                     [1,patches,dim] and the prefix tokens get no position row
     ls1.i ls2.i [dim]                                LayerScale (timm Block.ls1 / ls2 gamma; absent = none): x += ls1 * attn(...),
                                                      x += ls2 * mlp(...); kept fp32, never rounded
 
-N = patches + prefix_tokens: pos covers every token.  A model with two prefix tokens and no ``head_dist_w`` (HF
-``DeiTForImageClassification``) reads its head on CLS only.
+N = patches + prefix_tokens: pos covers every token, unless ``no_embed_class`` (N = patches then).  A model with two prefix tokens
+and no ``head_dist_w`` (HF ``DeiTForImageClassification``) reads its head on CLS only.  The head of a register model reads CLS.
 
 ``nn.Linear`` row-major ``[out,in]`` is kept as is: it is already the K-contiguous "B^T" layout
 the MFMA GEMM wants.  Anatomy adapters (``from_module``) accept the same three layouts the
@@ -85,18 +89,46 @@ VIT_CONFIGS = {
     "vit_small_patch14_dinov2_d2": (518, 14, 384, 6, 1536, 2),
     "vit_small_patch16_224_ls_d2": (224, 16, 384, 6, 1536, 2),
     "vit_test_patch16_32_ls": (32, 16, 64, 4, 128, 4),
+    # DeiT-III: class-free positions (NO_EMBED_CLASS below: pos has the patches' rows only) and LayerScale
+    "deit3_small_patch16_224": (224, 16, 384, 6, 1536, 12),
+    "deit3_base_patch16_224": (224, 16, 768, 12, 3072, 12),
+    "deit3_large_patch16_224": (224, 16, 1024, 16, 4096, 24),
+    "deit3_base_patch16_384": (384, 16, 768, 12, 3072, 12),
+    "deit3_small_patch16_224_d2": (224, 16, 384, 6, 1536, 2),
+    # DINOv2 with four register tokens between CLS and the patches (REG_TOKENS below), class-free positions and LayerScale: 1374 tokens
+    # at 518 pixels (the key-streaming attention), 261 at 224; and test cuts.  vit_test_patch16_32_reg4 has 4 + 5 = 9 tokens at d_h 16;
+    # vit_test_patch16_32_reg2_pe two registers with positions for every token (7 tokens), no LayerScale
+    "vit_small_patch14_reg4_dinov2": (518, 14, 384, 6, 1536, 12),
+    "vit_base_patch14_reg4_dinov2": (518, 14, 768, 12, 3072, 12),
+    "vit_large_patch14_reg4_dinov2": (518, 14, 1024, 16, 4096, 24),
+    "vit_small_patch14_reg4_dinov2_224": (224, 14, 384, 6, 1536, 12),
+    "vit_base_patch14_reg4_dinov2_224": (224, 14, 768, 12, 3072, 12),
+    "vit_large_patch14_reg4_dinov2_224": (224, 14, 1024, 16, 4096, 24),
+    "vit_small_patch14_reg4_dinov2_224_d2": (224, 14, 384, 6, 1536, 2),
+    "vit_small_patch14_reg4_dinov2_d2": (518, 14, 384, 6, 1536, 2),
+    "vit_test_patch16_32_reg4": (32, 16, 64, 4, 128, 4),
+    "vit_test_patch16_32_reg2_pe": (32, 16, 64, 4, 128, 4),
 }
 # VIT_CONFIGS entries with a distillation token and head (their entries stay (img, patch, dim, heads, d_int, depth))
 DISTILLED = frozenset(k for k in VIT_CONFIGS if k.startswith("deit_") and "_distilled_" in k)
 
 
 # VIT_CONFIGS entries whose blocks carry LayerScale (synthetic_weights draws ls1 / ls2 for them by default)
-LAYER_SCALE = frozenset(k for k in VIT_CONFIGS if "_dinov2" in k or k.endswith(("_ls", "_ls_d2")))
+LAYER_SCALE = frozenset(k for k in VIT_CONFIGS if "_dinov2" in k or k.endswith(("_ls", "_ls_d2")) or k.startswith("deit3_")
+                        or k == "vit_test_patch16_32_reg4")
+
+# VIT_CONFIGS entries with register tokens between CLS and the patches: name -> how many ("_reg<R>" in the name)
+REG_TOKENS = {k: int(k.split("_reg")[1][0]) for k in VIT_CONFIGS if "_reg" in k}
+
+# VIT_CONFIGS entries with class-free positions (timm no_embed_class=True: pos has the patches' rows only)
+NO_EMBED_CLASS = frozenset(k for k in VIT_CONFIGS if k.startswith("deit3_") or (k in REG_TOKENS and not k.endswith("_pe")))
+
+MAX_REG_TOKENS = 8                                      # the engine's limit (ssp2_create_layout)
 
 
 def prefix_tokens_of(name: str) -> int:
-    """Tokens in front of the patches of a VIT_CONFIGS model: 2 for the distilled DeiTs, else 1."""
-    return 2 if name in DISTILLED else 1
+    """Tokens in front of the patches of a VIT_CONFIGS model: 2 for the distilled DeiTs, 1 + R with R register tokens, else 1."""
+    return 2 if name in DISTILLED else 1 + REG_TOKENS.get(name, 0)
 
 
 def n_tokens(w: Dict) -> int:
@@ -113,6 +145,8 @@ def synthetic_weights(name: str = "vit_base_patch16_224", classes: int = 1000, s
     (SURVEY.md §8d).  ``layer_scale`` (default: the model is in LAYER_SCALE) adds ``ls1.i`` / ``ls2.i``: magnitudes log-uniform in
     [1e-3, 2], about a quarter of them negative — not the 1e-5 init value, so that a column-mapping error moves a result by far more
     than any tolerance.  They are drawn from a generator of their own: the other tensors are the same with and without them.
+    Models in REG_TOKENS get ``reg`` (trunc-normal(std), from a generator of its own as well); models in NO_EMBED_CLASS get
+    ``no_embed_class = True`` and a ``pos`` of the patches' rows only.
     """
     img, patch, dim, heads, inter, depth = VIT_CONFIGS[name]
     g = torch.Generator().manual_seed(seed)
@@ -133,7 +167,7 @@ def synthetic_weights(name: str = "vit_base_patch16_224", classes: int = 1000, s
     w["patch_w"] = tn(dim, 3, patch, patch)
     w["patch_b"] = bias(dim)
     w["cls"] = tn(1, 1, dim)
-    w["pos"] = tn(1, n_tok, dim)
+    w["pos"] = tn(1, n_tok - prefix if name in NO_EMBED_CLASS else n_tok, dim)
     for i in range(depth):
         w[f"ln1_g.{i}"] = torch.ones(dim); w[f"ln1_b.{i}"] = torch.zeros(dim)
         w[f"qkv_w.{i}"] = tn(3 * dim, dim); w[f"qkv_b.{i}"] = bias(3 * dim)
@@ -147,9 +181,16 @@ def synthetic_weights(name: str = "vit_base_patch16_224", classes: int = 1000, s
         w[f"fc2_w.{i}"] = tn(dim, inter); w[f"fc2_b.{i}"] = bias(dim)
     w["lnf_g"] = torch.ones(dim); w["lnf_b"] = torch.zeros(dim)
     w["head_w"] = tn(classes, dim); w["head_b"] = bias(classes)
-    if prefix == 2:
+    if name in DISTILLED:
         w["dist"] = tn(1, 1, dim)
         w["head_dist_w"] = tn(classes, dim); w["head_dist_b"] = bias(classes)
+    if name in NO_EMBED_CLASS:
+        w["no_embed_class"] = True
+    if name in REG_TOKENS:
+        gr = torch.Generator().manual_seed(seed + 104729)
+        reg = torch.empty(1, REG_TOKENS[name], dim)
+        torch.nn.init.trunc_normal_(reg, std=std, a=-2 * std, b=2 * std, generator=gr)
+        w["reg"] = reg
     if (name in LAYER_SCALE) if layer_scale is None else layer_scale:
         gl = torch.Generator().manual_seed(seed + 7919)
         lo, hi = math.log(1e-3), math.log(2.0)
@@ -194,25 +235,60 @@ def score_site_for(layout: str) -> str:
     return "pre_gelu" if layout == "timm" else "post_gelu"
 
 
-def _check_timm_token_layout(model) -> int:
-    """Prefix tokens of a timm-layout module (1, or 2 with `dist_token`), after refusing every layout the engine cannot represent:
-    register tokens, position embeddings without the prefix rows (`no_embed_class`), a pooled head (`global_pool` other than
-    'token', a `fc_norm` that is not Identity) and more than two prefix tokens."""
-    if getattr(model, "reg_token", None) is not None or int(getattr(model, "num_reg_tokens", 0) or 0) > 0:
-        raise ValueError("reg_token: register tokens are not supported (the engine's sequence is CLS [+ DIST] + patches)")
-    if getattr(model, "no_embed_class", False):
-        raise ValueError("no_embed_class: position embeddings without the prefix tokens' rows are not supported")
+def reg_tokens_of(w: Dict) -> int:
+    """Register tokens of a flat dictionary (rows of `reg`, 0 without it)."""
+    return int(w["reg"].shape[-2]) if w.get("reg") is not None else 0
+
+
+def _timm_reg_tokens(model) -> int:
+    """Register tokens of a timm-layout module: rows of `reg_token` [1, R, dim], checked against `num_reg_tokens`."""
+    reg = getattr(model, "reg_token", None)
+    nreg = getattr(model, "num_reg_tokens", None)
+    if reg is None:
+        if int(nreg or 0) > 0:
+            raise ValueError(f"reg_token: num_reg_tokens={int(nreg)} but the model has no reg_token parameter")
+        return 0
+    if reg.dim() != 3 or int(reg.shape[0]) != 1 or int(reg.shape[1]) < 1:
+        raise ValueError(f"reg_token: shape {tuple(reg.shape)} is not [1, R, dim]")
+    r = int(reg.shape[1])
+    if nreg is not None and int(nreg) != r:
+        raise ValueError(f"reg_token: {r} rows but num_reg_tokens={int(nreg)}")
+    if r > MAX_REG_TOKENS:
+        raise ValueError(f"reg_token: {r} register tokens, the engine takes up to {MAX_REG_TOKENS}")
+    return r
+
+
+def _check_timm_token_layout(model) -> Tuple[int, int, bool]:
+    """(prefix tokens, register tokens, no_embed_class) of a timm-layout module — CLS [+ dist_token], or CLS + up to 8 rows of
+    `reg_token`, with positions for every token or class-free (`no_embed_class`) — after refusing, by the attribute's name, every
+    layout the engine cannot represent and every set of attributes that does not agree with itself: registers or class-free
+    positions beside a `dist_token` (timm's distilled class has neither), `num_reg_tokens` without a `reg_token`, `no_embed_class`
+    on a `pos_embed` that is no square number of rows, a `num_prefix_tokens` that is not the count of the tokens found, a pooled
+    head (`global_pool` other than 'token', a `fc_norm` that is not Identity)."""
+    regs = _timm_reg_tokens(model)
+    dist = getattr(model, "dist_token", None) is not None
+    nec = bool(getattr(model, "no_embed_class", False))
+    if regs and dist:
+        raise ValueError("reg_token: register tokens beside a dist_token are not supported (timm's distilled models have none)")
+    if nec and dist:
+        raise ValueError("no_embed_class: class-free positions beside a dist_token are not supported (timm's distilled models have positions for every token)")
+    if nec:
+        rows = int(model.pos_embed.shape[1])
+        side = int(round(math.sqrt(rows)))
+        if side < 1 or side * side != rows:
+            raise ValueError(f"no_embed_class: True, but pos_embed has {rows} rows, which is no square number of patches")
     pool = getattr(model, "global_pool", "token")
     if pool not in ("token", None):
         raise ValueError(f"global_pool={pool!r}: only the token head ('token': the head reads CLS [+ DIST]) is supported")
     fcn = getattr(model, "fc_norm", None)
     if fcn is not None and not isinstance(fcn, torch.nn.Identity):
         raise ValueError(f"fc_norm: a {type(fcn).__name__} in front of the head is not supported (only Identity)")
-    prefix = 1 + (getattr(model, "dist_token", None) is not None)
+    prefix = 1 + regs + int(dist)
     npt = getattr(model, "num_prefix_tokens", None)
     if npt is not None and int(npt) != prefix:
-        raise ValueError(f"num_prefix_tokens={int(npt)}: the engine supports CLS or CLS + dist_token (1 or 2 prefix tokens)")
-    return prefix
+        raise ValueError(f"num_prefix_tokens={int(npt)}: the model has CLS{' + dist_token' if dist else ''}"
+                         f"{f' + {regs} register token(s)' if regs else ''} = {prefix} prefix token(s)")
+    return prefix, regs, nec
 
 
 def _timm_layer_scale(block, name: str, dim: int, where: str) -> Optional[torch.Tensor]:
@@ -283,15 +359,38 @@ def _hf_embeddings(emb, w: Dict) -> None:
 
 
 def _side_of(w: Dict) -> int:
-    """Patches per side from the position embedding (patches + prefix tokens rows); a count that is no square plus the prefix (position
-    embeddings without the prefix rows, extra tokens) is refused rather than misread."""
-    prefix = int(w.get("prefix_tokens", 1))
+    """Patches per side from the position embedding: patches + prefix tokens rows, or with `no_embed_class` the patches' rows only;
+    a count that does not fit the dictionary's reading is refused rather than misread."""
+    prefix = 0 if w.get("no_embed_class") else int(w.get("prefix_tokens", 1))
     n_tok = int(w["pos"].shape[1])
     side = int(round(math.sqrt(max(n_tok - prefix, 0))))
     if side < 1 or side * side + prefix != n_tok:
         raise ValueError(f"pos_embed: {n_tok} rows are not {prefix} prefix token(s) + a square number of patches "
-                         "(no_embed_class or extra tokens are not supported)")
+                         + ("(no_embed_class: the patches' rows only)" if w.get("no_embed_class") else "(extra tokens are not supported)"))
     return side
+
+
+def check_flat_layout(w: Dict) -> Tuple[int, int, bool]:
+    """(prefix_tokens, register tokens, no_embed_class) of a flat dictionary, validated: `reg` is [1, R, dim] with R <= 8 and
+    prefix_tokens = 1 + R, no `dist` / `head_dist_w` beside registers or class-free positions, and `pos` has `patches` rows
+    (no_embed_class) or `patches + prefix_tokens` (patches from img / patch)."""
+    regs, nec = reg_tokens_of(w), bool(w.get("no_embed_class", False))
+    prefix = int(w.get("prefix_tokens", 1))
+    if regs:
+        if w["reg"].dim() != 3 or int(w["reg"].shape[0]) != 1 or int(w["reg"].shape[2]) != int(w["dim"]):
+            raise ValueError(f"reg: shape {tuple(w['reg'].shape)} is not [1, R, {int(w['dim'])}]")
+        if regs > MAX_REG_TOKENS:
+            raise ValueError(f"reg: {regs} register tokens, the engine takes up to {MAX_REG_TOKENS}")
+        if prefix != 1 + regs:
+            raise ValueError(f"prefix_tokens={prefix}: CLS + {regs} register token(s) are {1 + regs}")
+    if (regs or nec) and (w.get("dist") is not None or "head_dist_w" in w or (not regs and prefix == 2)):
+        raise ValueError("dist: a distillation token or head beside register tokens (reg) or class-free positions (no_embed_class) is not supported")
+    patches = (int(w["img"]) // int(w["patch"])) ** 2
+    rows = int(w["pos"].shape[1])
+    if rows != (patches if nec else patches + prefix):
+        raise ValueError(f"no_embed_class={nec}: pos has {rows} rows, expected {patches if nec else patches + prefix} "
+                         f"({patches} patches{'' if nec else f' + {prefix} prefix token(s)'})")
+    return prefix, regs, nec
 
 
 def token_layout(model) -> tuple:
@@ -304,6 +403,15 @@ def token_layout(model) -> tuple:
     return (2 if dist else 1, int(dist and hasattr(model, "distillation_classifier")))
 
 
+def position_layout(model) -> tuple:
+    """(register tokens, no_embed_class) of a live module, read from its attributes without copying a weight: the part of the token
+    layout `token_layout` does not carry (the engine cache keys on both)."""
+    if detect_layout(model) != "timm":
+        return (0, False)
+    reg = getattr(model, "reg_token", None)
+    return (int(reg.shape[1]) if reg is not None and reg.dim() == 3 else 0, bool(getattr(model, "no_embed_class", False)))
+
+
 def from_module(model) -> Dict:
     """Extract the flat dictionary from a live module (weights are copied, the module is untouched).  Distilled DeiT (timm
     `dist_token` + `head_dist`; HF `distillation_token` + `cls_classifier` / `distillation_classifier`, or a CLS-only `classifier`)
@@ -311,12 +419,18 @@ def from_module(model) -> Dict:
     layout = detect_layout(model)
     w: Dict = {}
     if layout == "timm":
-        prefix = _check_timm_token_layout(model)
+        prefix, regs, nec = _check_timm_token_layout(model)
         pe = model.patch_embed.proj
         blocks = list(model.blocks)
         w["patch_w"], w["patch_b"] = _f32(pe.weight), _f32(pe.bias)
         w["cls"], w["pos"] = _f32(model.cls_token), _f32(model.pos_embed)
-        if prefix == 2:
+        if regs:
+            w["reg"], w["prefix_tokens"] = _f32(model.reg_token), prefix
+            if int(w["reg"].shape[2]) != int(w["cls"].shape[-1]):
+                raise ValueError(f"reg_token: shape {tuple(w['reg'].shape)} is not [1, R, {int(w['cls'].shape[-1])}]")
+        if nec:
+            w["no_embed_class"] = True
+        if prefix == 2 and not regs:
             w["dist"], w["prefix_tokens"] = _f32(model.dist_token), 2
             if getattr(model, "head_dist", None) is not None:
                 w["head_dist_w"], w["head_dist_b"] = _f32(model.head_dist.weight), _bias_or_zeros(model.head_dist)
@@ -438,14 +552,24 @@ def from_state_dict(sd: Dict[str, torch.Tensor], config: Optional[Dict] = None, 
                              "and the mean patch token); use the timm layout (blocks.N.ls1.gamma)")
     if has("patch_embed.proj.weight"):                                   # ---- timm
         layout = "timm"
-        for k, what in (("reg_token", "register tokens"), ("fc_norm.weight", "a LayerNorm in front of the head (fc_norm: pooled head)")):
-            if has(k):
-                raise ValueError(f"{k.split('.')[0]}: {what} not supported")
+        if has("fc_norm.weight"):
+            raise ValueError("fc_norm: a LayerNorm in front of the head (fc_norm: pooled head) not supported")
+        if has("reg_token") and has("dist_token"):
+            raise ValueError("reg_token: register tokens beside a dist_token are not supported (timm's distilled models have none)")
         w["patch_w"], w["patch_b"] = f("patch_embed.proj.weight"), f("patch_embed.proj.bias")
         w["cls"], w["pos"] = f("cls_token"), f("pos_embed")
+        dim = int(w["patch_w"].shape[0])
         if has("dist_token"):                                            # distilled DeiT: CLS + DIST, two heads averaged
             w["dist"], w["prefix_tokens"] = f("dist_token"), 2
-        dim = int(w["patch_w"].shape[0])
+        if has("reg_token"):                                             # register tokens: CLS + R rows
+            reg = f("reg_token")
+            if reg.dim() != 3 or int(reg.shape[0]) != 1 or int(reg.shape[2]) != dim or int(reg.shape[1]) < 1:
+                raise ValueError(f"reg_token: shape {tuple(reg.shape)} is not [1, R, {dim}]")
+            if int(reg.shape[1]) > MAX_REG_TOKENS:
+                raise ValueError(f"reg_token: {int(reg.shape[1])} register tokens, the engine takes up to {MAX_REG_TOKENS}")
+            w["reg"], w["prefix_tokens"] = reg, 1 + int(reg.shape[1])
+        if _infer_no_embed_class(w, config, meta):
+            w["no_embed_class"] = True
         i = 0
         while has(f"blocks.{i}.norm1.weight"):
             p = f"blocks.{i}."
@@ -549,6 +673,40 @@ def from_state_dict(sd: Dict[str, torch.Tensor], config: Optional[Dict] = None, 
     if meta.get("origin_layout"):
         w["origin_layout"] = meta["origin_layout"]
     return w
+
+
+def _infer_no_embed_class(w: Dict, config: Dict, meta: Dict) -> bool:
+    """A timm state dict cannot say `no_embed_class`; the row count of pos_embed can: class-free when `rows` is a square number of
+    patches, with the prefix rows when `rows - prefix` is one.  Where both hold (toy sizes: 9 rows with four registers, 25 with
+    eight) `no_embed_class` or the image size (`img_size` / `image_size`) of `config` / `meta` decides; without them the dictionary
+    is refused, naming both readings.  A distillation token rules the class-free reading out."""
+    prefix = int(w.get("prefix_tokens", 1))
+    rows = int(w["pos"].shape[1])
+    patch = int(w["patch_w"].shape[-1])
+    sq = lambda n: n >= 1 and int(round(math.sqrt(n))) ** 2 == n
+    free, full = sq(rows) and "dist" not in w, sq(rows - prefix)
+    for src in (config, meta):
+        if src.get("no_embed_class") is not None:
+            want = bool(src["no_embed_class"])
+            if not (free if want else full):
+                raise ValueError(f"pos_embed: {rows} rows do not fit no_embed_class={want} with {prefix} prefix token(s)")
+            return want
+    for src in (config, meta):
+        img = src.get("img_size", src.get("image_size"))
+        if isinstance(img, (list, tuple)):
+            img = img[0]
+        if img is not None:
+            patches = (int(img) // patch) ** 2
+            if rows == patches and free:
+                return True
+            if rows == patches + prefix and full:
+                return False
+            raise ValueError(f"pos_embed: {rows} rows fit neither {patches} patches (no_embed_class) nor {patches} + {prefix} prefix "
+                             f"token(s) at an image size of {int(img)}")
+    if free and full:
+        raise ValueError(f"pos_embed: {rows} rows read both as {rows} patches without the prefix tokens' rows (no_embed_class) and as "
+                         f"{rows - prefix} patches + {prefix} prefix token(s); give config img_size / image_size or no_embed_class")
+    return free and not full         # (neither: _side_of refuses the count by name)
 
 
 def load_checkpoint(path: str, heads: Optional[int] = None) -> Dict:

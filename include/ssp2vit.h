@@ -60,9 +60,9 @@ typedef struct ssp2_engine* ssp2_handle;
 
 typedef struct {
   int32_t img;          /* input resolution (square)                               */
-  int32_t patch;        /* patch size; tokens N = (img/patch)^2 + 1 (+ prefix_tokens instead of 1: ssp2_create_ext) */
+  int32_t patch;        /* patch size; tokens N = (img/patch)^2 + 1 (+ prefix_tokens instead of 1: ssp2_create_ext, ssp2_create_layout) */
   int32_t dim;          /* hidden size, multiple of 64                             */
-  int32_t heads;        /* dim/heads in {16, 64, 80}; tokens = (img/patch)^2 + 1 must fall into an instantiated key-tile count:
+  int32_t heads;        /* dim/heads in {16, 64, 80}; tokens = (img/patch)^2 + prefix tokens must fall into an instantiated key-tile count:
                          * d_h 64: up to 288 tokens (ViT-Ti/S/B/L at /16 and /32 up to 256 pixels; ViT-L/14); d_h 80: 257..288 (ViT-H/14);
                          * d_h 16: up to 32 — anything else is refused by ssp2_create with SSP2_EINVAL.  With SSP2_OPT_ATTN_STREAM >= 1
                          * (environment SSP2_ATTN_STREAM, or ssp2_create_opts) d_h 64 also takes 289..SSP2_ATTN_STREAM_MAX_TOKENS tokens
@@ -88,7 +88,8 @@ int ssp2_create_opts(const ssp2_vit_desc* desc, const int32_t* opt, ssp2_handle*
  * (deit_*_distilled_*: a CLS and a distillation token, tokens = patches + 2; in eval mode logits = (head(norm(x)[:, 0]) +
  * head_dist(norm(x)[:, 1])) / 2) and HF DeiTForImageClassification (the same two tokens, a head on CLS only).
  *   prefix_tokens  1 or 2: tokens in front of the patches.  Row 0 = cls + pos[0], row 1 = dist + pos[1] (SSP2_T_DIST); patch q is
- *                  token prefix_tokens + q.  pos (SSP2_T_POS) covers all tokens.
+ *                  token prefix_tokens + q.  pos (SSP2_T_POS) covers all tokens.  (Register tokens, class-free positions:
+ *                  ssp2_create_layout below.)
  *   dist_head      1: the logits are 0.5f * bf16(head(LN(row 0)) + head_dist(LN(row 1))) (SSP2_T_HEAD_DIST_W / _B), needs
  *                  prefix_tokens == 2; 0: the head reads row 0 only.
  * ssp2_tail* then carry the rows the head reads (2 with dist_head, else 1) through the last block; ssp2_head gathers them. */
@@ -98,6 +99,35 @@ typedef struct {
 } ssp2_vit_ext;
 /* ssp2_create_opts with a token layout; ext == NULL is ssp2_create_opts (and {1, 0} gives the same engine) */
 int ssp2_create_ext(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_vit_ext* ext, ssp2_handle* out);
+/* Additive (ABI stays 7): register tokens and class-free positions, the two switches of timm's VisionTransformer that DeiT-III
+ * (deit3_*: no_embed_class) and the DINOv2 register models (vit_*_patch14_reg4_dinov2: reg_tokens = 4, no_embed_class) set.  With
+ * P = prefix_tokens = 1 + reg_tokens and y the patch embedding (bf16 under autocast), timm's _pos_embed in eval mode gives
+ *   pos_prefix_rows = 1 (positions for every token, SSP2_T_POS = tokens * dim floats):
+ *       row 0 = cls + pos[0];  row r = reg[r - 1] + pos[r] (1 <= r < P);  row P + q = float(y[q]) + pos[P + q]
+ *   pos_prefix_rows = 0 (class-free positions, SSP2_T_POS = patches * dim floats; any other count is refused):
+ *       row 0 = cls;  row r = reg[r - 1];  row P + q = float(y[q]) + pos[q]      (the prefix rows are the fp32 parameters, no add)
+ * The stage-1 hook sums over all tokens (registers included); the head reads row 0, so the evaluation tail carries one row however
+ * many registers there are.  The token count must still meet an attention kernel (ssp2_vit_desc.heads).
+ *   prefix_tokens   1 + reg_tokens; with reg_tokens = 0: 1 or 2 as in ssp2_vit_ext
+ *   dist_head       as in ssp2_vit_ext; refused together with register tokens or class-free positions, as is a distillation token
+ *                   (prefix_tokens = 2 without registers) with class-free positions: timm's distilled class has neither
+ *   reg_tokens      0..8 register tokens between CLS and the patches, loaded with ssp2_set_reg_tokens
+ *   pos_prefix_rows 1 or 0, see above
+ * Every refusal is SSP2_EINVAL before the device is touched, naming the field.  ssp2_create_ext forwards here with reg_tokens = 0 and
+ * pos_prefix_rows = 1; layout == NULL is ssp2_create_opts.  ssp2_clone_weights refuses engines that differ in either new field and
+ * copies the register tokens; the operator entries (ssp2_attention_prefix_bf16: n_prefix 1..2) are as they were. */
+typedef struct {
+  int32_t prefix_tokens;
+  int32_t dist_head;
+  int32_t reg_tokens;
+  int32_t pos_prefix_rows;
+} ssp2_token_layout;
+int ssp2_create_layout(const ssp2_vit_desc* desc, const int32_t* opt, const ssp2_token_layout* layout, ssp2_handle* out);
+/* The register tokens of an engine created with reg_tokens = R > 0: fp32 [R, dim], host memory or (on_device != 0) HBM, held as fp32
+ * and never rounded (like the LayerScale vectors).  One copy into storage reserved at creation (no allocation here); a host source
+ * synchronises the handle's stream, a device source is asynchronous on it.  count != R (R = 0 included) or a null pointer is
+ * SSP2_EINVAL; ssp2_embed answers SSP2_ESTATE while R > 0 and the tokens were never set. */
+int ssp2_set_reg_tokens(ssp2_handle h, const float* reg, int count, int on_device);
 int ssp2_destroy(ssp2_handle h);
 int ssp2_set_stream(ssp2_handle h, void* hip_stream);
 /* Cap the grids of the handle's persistent kernels (large-tile GEMMs, d_h = 64 attention) at n_cu workgroups (<= 0 or
