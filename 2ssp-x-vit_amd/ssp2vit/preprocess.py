@@ -20,6 +20,10 @@ class GpuPreprocessor:
             raise Ssp2Error("ssp2vit needs an MI355X (HIP device): there is no CPU fallback in the product path")
         self.device = torch.device(device)
         self.in_h, self.in_w, self.out = int(in_hw[0]), int(in_hw[1]), int(out_size)
+        if self.in_h > 100 * self.in_w and self.out < self.in_h:
+            # Pillow's Image.resize swaps its passes for such images (vertical first); the kernels are horizontal-first, and the 8-bit
+            # image between the passes makes the two orders differ: this would not be the reference chain's result
+            raise ValueError(f"in_hw = {self.in_h} x {self.in_w}: heights above 100 widths that shrink are resized vertical-first by Pillow, which the device pipeline does not do")
         self.lib = _lib.load()
         m = (C.c_float * 3)(*[float(v) for v in mean])
         s = (C.c_float * 3)(*[float(v) for v in std])

@@ -478,7 +478,10 @@ int ssp2_layernorm(void* hip_stream, const float* x_dev, size_t in_stride, int r
  * 290-301): uint8 HWC images -> bicubic resize to out x out (Pillow's 8-bit fixed-point resampler, bit-identical) ->
  * optional horizontal flip of the resized image -> /255 -> (x - mean) / std -> fp32 NCHW.
  *   img_dev u8 [n, in_h, in_w, 3]; hflip_dev u8 [n] or NULL; tmp_dev u8 [n, in_h, out, 3] scratch;
- *   out_dev f32 [n, 3, out, out]; out_u8_dev u8 [n, out, out, 3] or NULL (the resized image itself, for checks). */
+ *   out_dev f32 [n, 3, out, out]; out_u8_dev u8 [n, out, out, 3] or NULL (the resized image itself, for checks: the bytes out_dev was
+ *   computed from, mirrored where hflip_dev says so).
+ *   The horizontal pass always runs first.  Pillow's Image.resize runs the vertical one first when in_h > 100 * in_w and out < in_h:
+ *   for such images the result is not Pillow's (ssp2vit.preprocess.GpuPreprocessor refuses them). */
 typedef struct ssp2_preproc* ssp2_preproc_handle;
 int ssp2_preproc_create(int in_h, int in_w, int out_size, const float* mean3, const float* std3, ssp2_preproc_handle* out);
 int ssp2_preproc_run(ssp2_preproc_handle p, void* hip_stream, const uint8_t* img_dev, int n, const uint8_t* hflip_dev,

@@ -587,6 +587,39 @@ def preprocess_cases():
     print("[golden] preprocess_pil.npz written (Pillow", PIL.__version__, ")")
 
 
+def preprocess_axis_cases():
+    """Pillow's resampler one axis at a time -> preprocess_pil_axes.npz (tests/preprocess_cases.py holds the lists).  The result along an
+    axis depends on that axis's (in, out) alone, so thin strips record it: a 6-line strip resized to (out, 6) runs the horizontal pass
+    only, its transpose resized to (6, out) the vertical pass only.  Lines 0-1 uniform bytes, 2-3 noise of 0 / 255 (both clips), 4 all 0,
+    5 all 255.  Four small whole images beside them, whose result depends on the 8-bit image between the passes: per geometry one
+    uniform, one noise, one with the upper rows 0 and the lower 255."""
+    import PIL
+    from PIL import Image
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import preprocess_cases as PC
+    rng = np.random.default_rng(22)
+    rec = {}
+    for n_in, n_out in PC.AXIS_PAIRS:
+        strip = np.empty((6, n_in, 3), dtype=np.uint8)
+        strip[0:2] = rng.integers(0, 256, size=(2, n_in, 3), dtype=np.uint8)
+        strip[2:4] = rng.integers(0, 2, size=(2, n_in, 3), dtype=np.uint8) * 255
+        strip[4], strip[5] = 0, 255
+        rec[f"axis.{n_in}.{n_out}.in"] = strip
+        rec[f"axis.{n_in}.{n_out}.h"] = np.asarray(Image.fromarray(strip).resize((n_out, 6), Image.BICUBIC))
+        rec[f"axis.{n_in}.{n_out}.v"] = np.asarray(Image.fromarray(np.ascontiguousarray(strip.transpose(1, 0, 2))).resize((6, n_out), Image.BICUBIC))
+    for h, w, s in PC.FULL_CASES:
+        imgs = np.empty((3, h, w, 3), dtype=np.uint8)
+        imgs[0] = rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
+        imgs[1] = rng.integers(0, 2, size=(h, w, 3), dtype=np.uint8) * 255
+        imgs[2, :h // 2], imgs[2, h // 2:] = 0, 255
+        rec[f"full.{h}.{w}.{s}.in"] = imgs
+        rec[f"full.{h}.{w}.{s}.out"] = np.stack([np.asarray(Image.fromarray(im).resize((s, s), Image.BICUBIC)) for im in imgs])
+    rec["pillow_version"] = np.asarray(PIL.__version__)
+    path = os.path.join(HERE, "preprocess_pil_axes.npz")
+    np.savez_compressed(path, **rec)
+    print(f"[golden] preprocess_pil_axes.npz written ({os.path.getsize(path)} bytes, Pillow {PIL.__version__})")
+
+
 def property_cases(n_planner=60, n_masks=60, n_oracle=25):
     """The reference's outputs on fixed seeded cases of tests/test_properties_cpu.py -> properties_reference.json + ref_head_<kind>.pt.
     The test module builds every case's inputs (imported from there, so both sides build the same ones) and runs the cases as explicit
@@ -648,6 +681,7 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--preprocess-only" in sys.argv:
         preprocess_cases()
+        preprocess_axis_cases()
         sys.exit(0)
     if "--b16-only" in sys.argv:
         vit_b16_case()
@@ -683,3 +717,4 @@ if __name__ == "__main__":
     heuristic_and_exports()
     artifact_tool_cases()
     preprocess_cases()
+    preprocess_axis_cases()
